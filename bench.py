@@ -10,7 +10,17 @@ MP_HSIR_Net(31,31,64,T=6), random init, synthetic 64x64x31 patches generated on 
 bf16 compute, one *full* training step per "step": forward, L1-after-clamp loss, backward, gradient
 all-reduce (RCCL, N>1), fused AdamW.  Weak scaling: per-GPU batch fixed.  Rank 0 prints one JSON line.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the line; nothing else runs on it.
+
+    --dump-outputs DIR   after the timed steps, rank 0 writes what the last timed step handed back as DIR/<name>.npy (float32):
+                         loss.npy (the returned loss) and params.npy (every parameter after the step's update, concatenated in
+                         named_parameters() order); --forward-only: restored.npy (the output).  An array of more than DUMP_MAX
+                         entries is written as a fixed seeded sample of DUMP_MAX.  Same arguments, same inputs: two builds can be
+                         compared output for output.  The forward is bitwise reproducible; the training step is not (the order of
+                         the backward's reductions varies), and over 25 steps loss and parameters spread by ~1e-3 rel-L2 run to run.
+    --full               also run the legs below (each still switched off by its --no-* option) and fill their objects.
+
+Extra objects on the line (--full; null otherwise):
   roofline     the dominant HIP kernel of the step: algorithmic FLOPs (or bytes) per launch / its mean
                launch duration, measured live with HIP events on the launch stream (mphsir_prof_*).
   roofline_spectral  the kernel north_star names: the spectral attention at 512x512x31 bf16 (forward of one test cube):
@@ -18,6 +28,8 @@ Extra objects on the line:
                the MFMA peak (N=1, rank 0).
   cpu_baseline the CPU oracle (a port of the reference's op sequence, oracle/mp_hsir_oracle.py) timed
                on this box's host cores on a bounded sample of the same workload (rank 0, N=1 only).
+  extra_configs  the other BASELINE.json configurations on the same code (N=1 only).
+  comm         the gradient all-reduce timed on its own (N>1).
 """
 import argparse
 import ctypes
@@ -68,7 +80,32 @@ def parse():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-spectral", action="store_true", help="skip the 512x512 spectral-attention roofline leg")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of replaying the captured step (hipGraph)")
+    ap.add_argument("--full", action="store_true", help="also run the roofline, spectral, CPU-baseline, extra-config and comm legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_MAX = 15 << 20             # entries kept per dumped array (60 MiB of float32; a fixed seeded sample beyond this)
+
+
+def _sample(flat):
+    """flat (1-D, on the device) -> float32 numpy; beyond DUMP_MAX entries a fixed seeded sample, in index order"""
+    if flat.numel() > DUMP_MAX:
+        idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX].sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.detach().float().cpu().numpy()
+
+
+def dump_outputs(path, out, net, training):
+    """what the last timed step handed back: the loss and, in place, the updated parameters (training), or the restored
+    batch (forward only)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if not training:
+        np.save(os.path.join(path, "restored.npy"), _sample(out.reshape(-1)))
+        return
+    np.save(os.path.join(path, "loss.npy"), out.detach().float().reshape(-1).cpu().numpy())
+    np.save(os.path.join(path, "params.npy"), _sample(torch.cat([p.detach().float().reshape(-1) for p in net.parameters()])))
 
 
 def cube_forward_worker(out_path, threads):
@@ -417,8 +454,9 @@ def main():
         step()
     fence()
     t0 = time.perf_counter()
+    out = None
     for _ in range(args.steps):
-        step()
+        out = step()
     fence()
     dt_s = time.perf_counter() - t0
     if world > 1:
@@ -426,8 +464,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt_s = float(t)
     value = world * args.batch * args.steps / dt_s
+    if args.dump_outputs and rank == 0 and out is not None:
+        dump_outputs(args.dump_outputs, out, net, not args.forward_only)
     comm = None
-    if world > 1 and not args.forward_only:
+    if args.full and world > 1 and not args.forward_only:
         # what the collective costs on its own: the gradient arena reduced bucket by bucket, as in a step, nothing else running
         fence()
         t0 = time.perf_counter()
@@ -441,7 +481,7 @@ def main():
                             else ("graph: one arena-wide all-reduce after the replay" if not args.no_graph else "eager: bucketed all-reduces from gradient hooks"))}
 
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # algorithmic work per step and per kernel (one accounted step), then per-kernel HIP-event timing (eager launches)
         if not args.forward_only:
             eng.force_eager = True          # same data flow (incl. the all-reduce for N > 1), individual launches
@@ -509,13 +549,13 @@ def main():
                                          round(acct[k][1] / v[1] / 1e9, 1)] for k, v in sorted(per.items()) if k in acct}}
 
     spectral = None
-    if rank == 0 and world == 1 and not args.no_roofline and not args.forward_only and args.dtype == "bf16" and not args.no_spectral \
+    if args.full and rank == 0 and world == 1 and not args.no_roofline and not args.forward_only and args.dtype == "bf16" and not args.no_spectral \
             and args.model == "natural_scene":
         eng.finish()
         torch.cuda.empty_cache()
         spectral = spectral_roofline(net, dev, lib)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "natural_scene" and not args.forward_only:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.model == "natural_scene" and not args.forward_only:
         # the oracle's 512x512 forward (20-30 s on 32 host threads) is started only now -- after the headline, the per-kernel and the
         # spectral legs -- as an ordinary child process: it overlaps the extra configurations below (each the best of two runs)
         import subprocess
@@ -525,7 +565,7 @@ def main():
                                       % (ROOT, cube_out, min(32, os.cpu_count() or 1))], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
 
     extra = None
-    if rank == 0 and world == 1 and not args.no_extra and not args.forward_only and args.model == "natural_scene" and args.dtype == "bf16":
+    if args.full and rank == 0 and world == 1 and not args.no_extra and not args.forward_only and args.model == "natural_scene" and args.dtype == "bf16":
         if spectral is None:
             eng.finish()
         del eng
@@ -533,7 +573,7 @@ def main():
         extra = extra_configs(dev)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cube_done = False
         if cube_proc is not None:                 # let it finish first: the timed legs below get the host to themselves
             try:

@@ -310,7 +310,7 @@ def test_bench_two_ranks_gloo_on_one_gpu(tmp_path):
     env = dict(os.environ, MPHSIR_DIST_BACKEND="gloo", MPHSIR_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "3", "--batch", "4",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=800)
+                        "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["config"]["global_batch"] == 8 and line["roofline"] is not None
@@ -333,7 +333,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "3", "--batch", "4",
-                        "--no-cpu-baseline", "--no-roofline"], env=dict(env, MPHSIR_DIST_BACKEND="gloo", MPHSIR_SHARE_GPU="1"),
+                        "--full", "--no-cpu-baseline", "--no-roofline"], env=dict(env, MPHSIR_DIST_BACKEND="gloo", MPHSIR_SHARE_GPU="1"),
                        capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -342,6 +342,32 @@ def test_bench_starts_its_own_ranks(tmp_path):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1"], env=env, capture_output=True,
                            text=True, timeout=300)
         assert r.returncode != 0 and "GPU(s) visible" in r.stderr and not r.stdout.strip()
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """a plain `bench.py` run times only the headline step (the --full legs stay null) and --dump-outputs writes the last step's
+    loss and updated parameters as finite float32 .npy files, 64 MB at most"""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    from mp_hsir_amd.net.MP_HSIR import MP_HSIR_Net
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert all(line[k] is None for k in ("roofline", "roofline_spectral", "cpu_baseline", "extra_configs", "comm"))
+    assert sorted(os.listdir(out)) == ["loss.npy", "params.npy"]
+    loss, params = np.load(out / "loss.npy"), np.load(out / "params.npy")
+    assert loss.dtype == np.float32 and params.dtype == np.float32 and np.isfinite(loss).all() and np.isfinite(params).all()
+    assert params.size == sum(v.numel() for v in MP_HSIR_Net(in_channel=31, out_channel=31, dim=64, task_classes=6,
+                                                              clip_prompt="surrogate").parameters())
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64e6
 
 
 def test_training_step_bf16_natural_runs_and_learns():
