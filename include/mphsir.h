@@ -557,6 +557,37 @@ int mphsir_cl_to_nchw_add(const void* Y, int64_t ldy, const float* R, float* O, 
 int mphsir_task_weights(const int64_t* ids, float* w, int32_t B, int32_t n, int32_t T, void* stream);
 int mphsir_mix_rows(const float* A, const float* Bm, float* O, int32_t I, int32_t J, int32_t D, float scale, int32_t transA, void* stream);
 
+/* ---- whole-scene inference: overlap tiles of a scene cut and blended on the device (mp-hsir_amd/scene.py; the reference has no tiled
+ * path: test.py crops every cube to multiples of 64 and runs one forward) -----------------------------------------------------
+ * mphsir_scene_gather: tiles [n][C][th][tw] fp32 = scene [C][H][W] fp32 cut at the n origins (oy, ox) of `origins` (DEVICE int32 pairs,
+ *   [n][2]; entries may repeat).  Element (u, v) of tile t reads scene row m(oy_t + u, H) and column m(ox_t + v, W), with m the mirror
+ *   map of torch's `reflect` padding (m(y, H) = -y for y < 0, 2(H-1) - y for y >= H, folded again if that still lies outside): any
+ *   origin is legal, negative and overhanging ones included.  th, tw multiples of 4 (tile rows are written as 16-byte vectors).
+ * mphsir_scene_blend:  scene [C][H][W] fp32 = the weighted mean of the ny * nx tiles [iy * nx + ix][C][th][tw] fp32 at the origins
+ *   oy [ny], ox [nx] (DEVICE int32).  Per axis a tile at origin o weighs its local coordinate u with
+ *       w(u) = min(1, (u + 1) / (ov + 1) if o > 0, (th - u) / (ov + 1) if o + th < H)          (no ramp on a side at the scene border)
+ *   the 2-D weight is wy * wx, and every pixel is sum(w * tile) / sum(w) over the tiles that cover it, taken in ascending tile number
+ *   in fp32.  A gather: each output pixel scans the origin arrays for its tiles -- no atomics, deterministic, normalised in the same
+ *   launch, tile positions outside the scene are never read.  clamp01 != 0 clamps the result to [0, 1].  A pixel that no tile
+ *   covers comes out NaN.  th, tw multiples of 4, 0 <= ov.                                                                      */
+typedef struct mphsir_scene_gather_args {
+    uint32_t struct_size;
+    const float* scene;
+    const int32_t* origins;
+    float* tiles;
+    int32_t n, C, H, W, th, tw;
+} mphsir_scene_gather_args;
+int mphsir_scene_gather(const mphsir_scene_gather_args* a, void* stream);
+typedef struct mphsir_scene_blend_args {
+    uint32_t struct_size;
+    const float* tiles;
+    const int32_t* oy;
+    const int32_t* ox;
+    float* scene;
+    int32_t ny, nx, C, H, W, th, tw, ov, clamp01;
+} mphsir_scene_blend_args;
+int mphsir_scene_blend(const mphsir_scene_blend_args* a, void* stream);
+
 /* ---- fused AdamW over the flat parameter arena ---------------------------------------------------
  * One decoupled-weight-decay Adam step on n contiguous fp32 parameters (n % 4 == 0) with gradient g,
  * moments m, v; g is multiplied by grad_scale first (1/world_size after a sum all-reduce).
@@ -651,7 +682,8 @@ int mphsir_l1_clamp_loss(const float* y, const float* clean, float* grad, float*
 #define MPHSIR_K_GATED_MLP_WGRAD 29
 #define MPHSIR_K_SPECTRAL_DQKV_BWD 30
 #define MPHSIR_K_LAYOUT 31
-#define MPHSIR_K_COUNT 32
+#define MPHSIR_K_SCENE 32
+#define MPHSIR_K_COUNT 33
 int mphsir_prof_enable(int kid);   /* kid < 0 disables */
 int mphsir_prof_read(int* launches, float* total_ms);
 const char* mphsir_kernel_name(int kid);

@@ -134,6 +134,17 @@ class SpectralBwdArgs(_Args):
                       ("part", c_void_p)] + [(n, c_int32) for n in ("B", "H", "W", "C", "heads", "nblk", "round_dall")] + [("vscale", c_void_p)]
 
 
+class SceneGatherArgs(_Args):
+    """mirror of struct mphsir_scene_gather_args"""
+    _fields_ = _SZ + [("scene", c_void_p), ("origins", c_void_p), ("tiles", c_void_p)] + [(n, c_int32) for n in ("n", "C", "H", "W", "th", "tw")]
+
+
+class SceneBlendArgs(_Args):
+    """mirror of struct mphsir_scene_blend_args"""
+    _fields_ = _SZ + [("tiles", c_void_p), ("oy", c_void_p), ("ox", c_void_p), ("scene", c_void_p)] + \
+               [(n, c_int32) for n in ("ny", "nx", "C", "H", "W", "th", "tw", "ov", "clamp01")]
+
+
 class TnProblem(ctypes.Structure):
     """mirror of struct mphsir_gemm_tn_problem"""
     _fields_ = [("A", c_void_p), ("lda", c_int64), ("B", c_void_p), ("ldb", c_int64), ("Cpart", c_void_p), ("colsum_part", c_void_p),
@@ -233,6 +244,8 @@ _SYMBOLS = {
     "mphsir_cl_to_nchw_add": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int, c_void_p]),
     "mphsir_task_weights": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "mphsir_mix_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p]),
+    "mphsir_scene_gather": (c_int, [ctypes.POINTER(SceneGatherArgs), c_void_p]),
+    "mphsir_scene_blend": (c_int, [ctypes.POINTER(SceneBlendArgs), c_void_p]),
     "mphsir_l1_clamp_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
 }
 

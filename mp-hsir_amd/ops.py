@@ -717,6 +717,44 @@ def mix_rows(A, Bm, scale, transA=False):
     return o
 
 
+def scene_gather_tiles(scene, origins, th, tw, out=None):
+    """scene (C,H,W) fp32, origins (n,2) int32 rows (oy, ox) on the device -> (n,C,th,tw) fp32 tiles (into `out`, if given), with
+    torch's `reflect` mirror map wherever a tile leaves the scene (any origin; one launch, mp-hsir_amd/scene.py)."""
+    lib = _lib.load()
+    _check(scene, origins, out)
+    assert scene.dim() == 3 and scene.dtype == torch.float32 and scene.is_contiguous()
+    assert origins.dim() == 2 and origins.shape[1] == 2 and origins.dtype == torch.int32 and origins.is_contiguous()
+    C, H, W = scene.shape
+    n = origins.shape[0]
+    if out is None:
+        out = torch.empty((n, C, th, tw), dtype=torch.float32, device=scene.device)
+    assert out.shape == (n, C, th, tw) and out.dtype == torch.float32 and out.is_contiguous() and out.device == scene.device
+    a = _lib.SceneGatherArgs(scene=_p(scene), origins=_p(origins), tiles=_p(out), n=n, C=C, H=H, W=W, th=th, tw=tw)
+    _lib.check(lib.mphsir_scene_gather(ctypes.byref(a), _stream(scene)), "scene_gather")
+    _acct("scene", 0.0, 8.0 * out.numel())
+    return out
+
+
+def scene_blend_tiles(tiles, oy, ox, ov, H, W, clamp01=False, out=None):
+    """tiles (ny*nx,C,th,tw) fp32 numbered iy * nx + ix, per-axis origins oy (ny,), ox (nx,) int32 on the device -> (C,H,W) fp32:
+    every pixel the ramp-weighted mean of the tiles that cover it (the weights: include/mphsir.h), one deterministic launch."""
+    lib = _lib.load()
+    _check(tiles, oy, ox, out)
+    assert tiles.dim() == 4 and tiles.dtype == torch.float32 and tiles.is_contiguous()
+    assert oy.dim() == 1 and ox.dim() == 1 and oy.dtype == ox.dtype == torch.int32 and oy.is_contiguous() and ox.is_contiguous()
+    n, C, th, tw = tiles.shape
+    ny, nx = oy.shape[0], ox.shape[0]
+    assert n == ny * nx, "tile store holds %d tiles, the origin arrays describe %d x %d" % (n, ny, nx)
+    if out is None:
+        out = torch.empty((C, H, W), dtype=torch.float32, device=tiles.device)
+    assert out.shape == (C, H, W) and out.dtype == torch.float32 and out.is_contiguous() and out.device == tiles.device
+    a = _lib.SceneBlendArgs(tiles=_p(tiles), oy=_p(oy), ox=_p(ox), scene=_p(out), ny=ny, nx=nx, C=C, H=H, W=W, th=th, tw=tw, ov=ov,
+                            clamp01=1 if clamp01 else 0)
+    _lib.check(lib.mphsir_scene_blend(ctypes.byref(a), _stream(tiles)), "scene_blend")
+    _acct("scene", 0.0, 4.0 * (tiles.numel() + out.numel()))
+    return out
+
+
 def round_up(n, m):
     return (n + m - 1) // m * m
 

@@ -1,0 +1,146 @@
+"""Whole-scene restoration: a scene of any extent goes through the network as overlapping tiles and comes back whole.
+
+The reference evaluates one forward over a cube centre-cropped to multiples of 64 (test.py / utils/image_utils.py:58-70) and has no
+tiled path.  Here the scene stays as it is: `plan_tiles` lays tiles over it (host, pure Python), `mphsir_scene_gather` cuts a batch
+of them on the device (mirror padding where a scene is smaller than one tile), the network restores the batch, and one
+`mphsir_scene_blend` launch folds all restored tiles back with linear ramps across the overlaps (mp-hsir_amd/csrc/scene.hip).
+
+Tile plan, per axis of extent H with requested tile T and nominal overlap ov:
+    th = min(T, round_up(H, grain))
+    H <= th: one tile at origin 0; its rows H..th-1 are mirror padding (source row 2(H-1) - y, at most grain - 1 < H of them)
+    else:    n = ceil((H - ov) / (th - ov)) tiles at origins (i * (H - th)) // (n - 1): evenly spread, first at 0, last ending at H,
+             neighbours overlapping by at least ov, nothing padded, at most 3 tiles over any pixel
+The tiles of a scene are the outer product of the two axes, numbered iy * nx + ix.
+
+Batching tiles is exact for this model, for a reason of its own: TVSP samples row floor(i * B / ps) of the (B,512) CLIP prompt, so
+a sample's prompt map depends on the batch around it -- but when every sample of the batch carries the SAME task id all
+B rows are equal and the map is the one a batch of 1 gets.  Every other operation of the network is per sample.  So one scene is one
+task id, and a batch of mixed ids is refused.
+"""
+import torch
+
+from . import ops
+
+GRAINS = (32, 64)       # 64: what test.py crops to; 32: the network's own limit (8-pixel windows on the coarsest of its three 2x levels)
+
+
+def _round_up(n, m):
+    return (n + m - 1) // m * m
+
+
+def plan_axis(H, T, ov, grain=64):
+    """-> (tile extent th, [origins]) of one axis: see the module docstring.  ValueError for anything it does not cover."""
+    if grain not in GRAINS:
+        raise ValueError("grain %r: only %s are supported" % (grain, GRAINS))
+    H, T, ov = int(H), int(T), int(ov)
+    if T <= 0 or T % grain:
+        raise ValueError("tile %d is not a positive multiple of %d" % (T, grain))
+    if not 0 <= ov <= T // 2:
+        raise ValueError("overlap %d outside [0, tile // 2 = %d]" % (ov, T // 2))
+    if H < grain:
+        raise ValueError("scene extent %d is smaller than %d" % (H, grain))
+    th = min(T, _round_up(H, grain))
+    if H <= th:
+        return th, [0]
+    n = -(-(H - ov) // (th - ov))
+    return th, [(i * (H - th)) // (n - 1) for i in range(n)]
+
+
+class TilePlan:
+    """th, tw: tile extent; oy, ox: per-axis origins; origins: (oy, ox) of tile iy * nx + ix"""
+
+    def __init__(self, H, W, th, tw, oy, ox, ov):
+        self.H, self.W, self.th, self.tw, self.oy, self.ox, self.ov = H, W, th, tw, list(oy), list(ox), ov
+        self.ny, self.nx = len(self.oy), len(self.ox)
+        self.origins = [(y, x) for y in self.oy for x in self.ox]
+
+    def __len__(self):
+        return self.ny * self.nx
+
+
+def plan_tiles(H, W, tile, ov, grain=64):
+    th, oy = plan_axis(H, tile, ov, grain)
+    tw, ox = plan_axis(W, tile, ov, grain)
+    return TilePlan(int(H), int(W), th, tw, oy, ox, int(ov))
+
+
+class SceneRestorer:
+    """restorer(scene, task_id) -> restored scene: tiled inference with on-device gather and blend.
+
+    net          MP_HSIR_Net, or any callable (x (B,C,th,tw) fp32, ids (B,) int64) -> (B,C,th,tw) fp32
+    tile         requested tile extent.  Default 256: an extent the GPU suite already runs whole, and a 4x bilinear stretch of the
+                 64x64 prompt map per side (the model is trained on 64x64 patches; TVSP resizes its prompt to whatever arrives)
+                 instead of the 8x of a 512 cube.
+    overlap      nominal overlap of neighbouring tiles, blended with linear ramps
+    tile_batch   tiles per forward; the last batch of a scene is filled by repeating its last tile, so one shape serves them all
+    graphed      an nn.Module is run through engine.GraphedForward (one capture for the one (tile_batch, C, th, tw) shape)
+    grain        tile extents are multiples of it: 64 (test.py's crop granularity), or 32 (the network's own limit)
+
+    A tile sees the TILE's global spectral attention (the channel Gram is taken over the tile) and the tile's prompt stretch, not
+    the scene's: tiled and whole-cube inference are two different functions of the input and are not expected to agree closely.
+    A scene that is exactly one tile runs the same path with a batch of 1 and equals the plain forward bit for bit.
+    """
+
+    def __init__(self, net, tile=256, overlap=32, tile_batch=4, graphed=True, grain=64):
+        plan_axis(tile, tile, overlap, grain)        # argument check only (ValueError)
+        if tile_batch < 1:
+            raise ValueError("tile_batch %r" % (tile_batch,))
+        self.tile, self.overlap, self.tile_batch, self.grain = tile, overlap, int(tile_batch), grain
+        if graphed and isinstance(net, torch.nn.Module):
+            from .engine import GraphedForward
+            net = GraphedForward(net)
+        self.forward = net
+        self._plans = {}           # (H, W, device) -> plan + its device origin arrays
+        self._buffers = {}         # (plan key, C) -> static tile-batch input, task ids, restored-tile store
+
+    def plan(self, H, W):
+        return plan_tiles(H, W, self.tile, self.overlap, self.grain)
+
+    def _device_plan(self, H, W, dev):
+        key = (H, W, str(dev))
+        e = self._plans.get(key)
+        if e is None:
+            p = self.plan(H, W)
+            B = min(self.tile_batch, len(p))
+            rows = p.origins + [p.origins[-1]] * (-len(p) % B)              # the tail batch repeats the last tile
+            e = self._plans[key] = (p, B, torch.tensor(rows, dtype=torch.int32, device=dev).reshape(-1, 2),
+                                    torch.tensor(p.oy, dtype=torch.int32, device=dev), torch.tensor(p.ox, dtype=torch.int32, device=dev))
+        return e
+
+    def _static_buffers(self, H, W, C, dev, B, p):
+        key = (H, W, str(dev), C)
+        e = self._buffers.get(key)
+        if e is None:
+            self._buffers.clear()          # scenes of one shape follow each other; another shape releases the last one's store
+            e = self._buffers[key] = (torch.empty((B, C, p.th, p.tw), dtype=torch.float32, device=dev),
+                                      torch.empty((B,), dtype=torch.int64, device=dev),
+                                      torch.empty((len(p), C, p.th, p.tw), dtype=torch.float32, device=dev))
+        return e
+
+    @torch.no_grad()
+    def __call__(self, scene, task_id, return_tiles=False):
+        """scene (C,H,W) or (1,C,H,W) fp32 on the GPU, task_id one int (or a 1-element tensor) -> restored, of the scene's shape.
+        return_tiles (debugging): -> (restored, the (n,C,th,tw) restored tiles the blend read: the restorer's own store, overwritten
+        by its next call)."""
+        if torch.is_tensor(task_id):
+            if task_id.numel() != 1:
+                raise ValueError("one scene is restored under one task id (got %d): tiles are batched, and TVSP's prompt map is "
+                                 "batch-invariant only when all samples of a batch share the id" % task_id.numel())
+            task_id = int(task_id.reshape(-1)[0])
+        if scene.dim() not in (3, 4) or (scene.dim() == 4 and scene.shape[0] != 1) or scene.dtype != torch.float32:
+            raise ValueError("scene must be (C,H,W) or (1,C,H,W) fp32, got %s %s" % (tuple(scene.shape), scene.dtype))
+        s3 = scene.reshape(scene.shape[-3:]).contiguous()
+        C, H, W = s3.shape
+        p, B, origins, oy, ox = self._device_plan(H, W, s3.device)
+        n = len(p)
+        xin, ids, store = self._static_buffers(H, W, C, s3.device, B, p)
+        ids.fill_(int(task_id))
+        for k in range(0, n, B):
+            ops.scene_gather_tiles(s3, origins[k:k + B], p.th, p.tw, out=xin)
+            y = self.forward(xin, ids)
+            valid = min(B, n - k)
+            if y.shape != xin.shape or y.dtype != torch.float32:
+                raise RuntimeError("the network returned %s %s for tiles %s" % (tuple(y.shape), y.dtype, tuple(xin.shape)))
+            store[k:k + valid].copy_(y[:valid])
+        out = ops.scene_blend_tiles(store, oy, ox, p.ov, H, W).reshape(scene.shape)
+        return (out, store) if return_tiles else out

@@ -17,12 +17,17 @@ forward under no_grad, band-wise PSNR / SSIM on the device (metrics.py = utils/v
   11    Poisson noise scale 10 (:243-275)                                  0
   12    real degraded / clean pairs from --test_degrad_dir (:197-241)      1
 
-Test cubes: --test_dir with .mat ('data' key, as the reference) or .npy cubes, centre-cropped to multiples of 64
-(crop_img, utils/image_utils.py:58-70); without it, synthetic cubes (no datasets offline).  The degradations are the
-GPU functions of degrade.py.  --ckpt_path evaluates a Lightning checkpoint of the reference (`net.` key prefix).
+Test cubes: --test_dir with .mat ('data' key, as the reference) or .npy cubes; without it, synthetic cubes (no datasets offline).
+Without --tile every cube is centre-cropped to multiples of 64 (crop_img, utils/image_utils.py:58-70) and restored in one forward,
+as the reference does.  With --tile N (an addition: the reference has no tiled path) cubes are NOT cropped: the degradation runs on
+the whole cube, restoration goes through scene.SceneRestorer (overlapping N x N tiles, --tile_overlap, gathered and blended on the
+GPU) and PSNR / SSIM are taken over the whole scene.  --save_restored 1 writes <output_path>/<mode label>/restored_<name>.npy
+(fp32, (C,H,W)) in either case.  The degradations are the GPU functions of degrade.py.  --ckpt_path evaluates a Lightning
+checkpoint of the reference (`net.` key prefix).
 """
 import argparse
 import os
+import re
 import sys
 
 import numpy as np
@@ -34,6 +39,7 @@ from mp_hsir_amd import degrade as D  # noqa: E402
 from mp_hsir_amd.engine import GraphedForward  # noqa: E402
 from mp_hsir_amd.metrics import compute_psnr_ssim, compute_psnr_ssim2  # noqa: E402
 from mp_hsir_amd.net.MP_HSIR import MP_HSIR_Net  # noqa: E402
+from mp_hsir_amd.scene import SceneRestorer  # noqa: E402
 
 
 def psnr_bandwise(restored, clean):
@@ -69,6 +75,10 @@ def build_parser():
     p.add_argument("--cubes", type=int, default=4)
     p.add_argument("--precision", type=str, default="f32", choices=["bf16", "f32"])
     p.add_argument("--allow_surrogate_clip", type=int, default=0)
+    p.add_argument("--tile", type=int, default=0, help="0: crop to multiples of 64 and restore the cube in one forward (the reference); "
+                   "N (a multiple of 64): keep the whole scene and restore it as overlapping N x N tiles")
+    p.add_argument("--tile_overlap", type=int, default=32, help="nominal overlap of neighbouring tiles (at most tile // 2)")
+    p.add_argument("--save_restored", type=int, default=0, help="1: write <output_path>/<mode label>/restored_<name>.npy (fp32, (C,H,W))")
     return p
 
 
@@ -87,17 +97,20 @@ def load_cube(path):
 
 
 def cube_source(o, bands, dev, gen):
-    """yields (name, clean (1,C,H,W) on dev[, real degraded])"""
+    """yields (name, clean (1,C,H,W) on dev[, real degraded]); cropped to multiples of 64 unless --tile keeps the whole scene"""
+    crop = (lambda x: x) if o.tile > 0 else crop_img
     if o.test_dir:
         for fn in sorted(os.listdir(o.test_dir)):
-            clean = torch.from_numpy(crop_img(load_cube(os.path.join(o.test_dir, fn)))).to(dev)[None]
+            clean = torch.from_numpy(crop(load_cube(os.path.join(o.test_dir, fn)))).to(dev)[None]
             real = None
             if o.mode == 12:
-                real = torch.from_numpy(crop_img(load_cube(os.path.join(o.test_degrad_dir, fn)))).to(dev)[None]
+                real = torch.from_numpy(crop(load_cube(os.path.join(o.test_degrad_dir, fn)))).to(dev)[None]
             yield fn.split(".")[0], clean, real
     else:
         if o.mode == 12:
             raise SystemExit("mode 12 evaluates real degraded/clean pairs: pass --test_dir and --test_degrad_dir")
+        if o.tile > 0 and o.size < 64:
+            raise SystemExit("--size %d: a synthetic cube must be at least 64 x 64" % o.size)
         for i in range(o.cubes):
             yield "synthetic_%d" % i, torch.rand((1, bands, o.size, o.size), generator=gen, device=dev), None
 
@@ -157,20 +170,51 @@ MODE_LABEL = {0: "Denoise sigma=%(gaussian_noise_sigma)s", 1: "Denoise sigma=%(g
               11: "Degrad_Id=%(degrad_id)s", 12: "Degrad_Id=%(degrad_id)s"}
 
 
+def mode_dir(o):
+    """directory name of a run's outputs under --output_path: the mode's label line with everything but [A-Za-z0-9=.,-] folded to _"""
+    return re.sub(r"[^A-Za-z0-9=.,-]+", "_", MODE_LABEL[o.mode] % vars(o)).strip("_")
+
+
+def check_whole_scene(o, name, clean):
+    """with --tile cubes keep their extent, so a degradation with a divisibility need of its own is checked before it runs"""
+    H, W = clean.shape[-2:]
+    if min(H, W) < 64:
+        raise SystemExit("cube %s is %d x %d: smaller than 64 x 64" % (name, H, W))
+    if o.mode == 7 and (H % o.downsample_factor or W % o.downsample_factor):
+        raise SystemExit("cube %s is %d x %d: mode 7 downsamples by --downsample_factor %d, which does not divide both extents "
+                         "(crop the cube, or run without --tile)" % (name, H, W, o.downsample_factor))
+
+
 def evaluate(o, net, dev):
     """-> (mean psnr, mean ssim, number of cubes); prints one line per cube"""
     cfg_bands = net.patch_embed.proj.weight.shape[1]
     gen = torch.Generator(device=dev).manual_seed(o.seed)
     d = D.Draws(dev, o.seed + 1)
-    run = GraphedForward(net)            # cubes of one shape: captured after two eager calls, then replayed
+    if o.tile > 0:
+        try:
+            run = SceneRestorer(net, tile=o.tile, overlap=o.tile_overlap)   # tiles of one shape: one captured forward serves every scene
+        except ValueError as e:
+            raise SystemExit("--tile %d --tile_overlap %d: %s" % (o.tile, o.tile_overlap, e))
+    else:
+        run = GraphedForward(net)        # cubes of one shape: captured after two eager calls, then replayed
+    out_dir = os.path.join(o.output_path, mode_dir(o))
+    if o.save_restored:
+        os.makedirs(out_dir, exist_ok=True)
     ps = ss = 0.0
     n = 0
     for name, clean, real in cube_source(o, cfg_bands, dev, gen):
+        if o.tile > 0:
+            check_whole_scene(o, name, clean)
         if o.mode == 12:
             degraded, pid = real, 1
         else:
             degraded, pid = degrade_for_mode(o, clean, d, o.model)
-        restored = run(degraded.float().contiguous(), torch.tensor([pid], device=dev))
+        if o.tile > 0:
+            restored = run(degraded.float().contiguous(), pid)
+        else:
+            restored = run(degraded.float().contiguous(), torch.tensor([pid], device=dev))
+        if o.save_restored:
+            np.save(os.path.join(out_dir, "restored_%s.npy" % name), restored[0].float().cpu().numpy())
         clean_c = clean.clamp(0, 1)
         if o.mode == 10:
             p, s, cnt = compute_psnr_ssim2(restored, clean_c, degraded)      # only the completed bands (test.py:523)
