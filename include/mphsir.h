@@ -588,6 +588,37 @@ typedef struct mphsir_scene_blend_args {
 } mphsir_scene_blend_args;
 int mphsir_scene_blend(const mphsir_scene_blend_args* a, void* stream);
 
+/* ---- scene quality: band-wise PSNR / SSIM and the mean spectral angle of a restored cube against the clean one, one launch pair --------
+ * restored, clean: [B][C][H][W] fp32, contiguous, H >= 7, W >= 7.  Both are clipped to [0, 1] first (x < 0 ? 0 : x > 1 ? 1 : x, so a NaN
+ * stays a NaN and poisons what it enters); everything after the clip is float64.
+ *   psnr [B][C]   = 10 log10(1 / mse), mse = mean over H W of (x - y)^2; mse == 0 gives +inf            (skimage peak_signal_noise_ratio,
+ *                   data_range 1: the reference's utils/val_utils.py:49-105)
+ *   ssim [B][C]   = skimage structural_similarity with its defaults at data_range 1: uniform 7 x 7 window, sample covariance
+ *                   (cov_norm 49/48), c1 = 1e-4, c2 = 9e-4, the mean over the (H - 6)(W - 6) windows that lie wholly inside the band
+ *   sam_deg [B], sam_pixels [B]: per pixel, over its C clipped values, nx = sqrt(sum x^2), ny = sqrt(sum y^2), d2 = sum (x - y)^2 and
+ *                   theta = 2 atan2( sqrt(max(d2 - (nx - ny)^2, 0)), sqrt(max((nx + ny)^2 - d2, 0)) )
+ *                   -- the half-angle form of arccos(<x,y> / (nx ny)): exactly 0 for identical spectra, no cancellation at small angles.
+ *                   Pixels with nx == 0 or ny == 0 have no angle and are left out; sam_pixels counts the pixels that are in, sam_deg is
+ *                   their mean theta in degrees (0 when none is in).  The reference has no spectral-angle metric.
+ * Deterministic: no atomics, block partials combined in a fixed order -- bitwise equal from run to run.  No cube-sized temporary: the
+ * only scratch is `workspace`, mphsir_quality_workspace_bytes(B, C, H, W) bytes (8-byte aligned, caller-owned; 16 (C + 1) bytes per
+ * 32 x 32 pixel block and image), which the first launch fills and the second reads.  Index range: B <= 65535, C <= 65535,
+ * H * W < 2^31; the size query returns a negative value for sizes mphsir_quality refuses.                                          */
+typedef struct mphsir_quality_args {
+    uint32_t struct_size;
+    const float* restored;
+    const float* clean;
+    double* psnr;
+    double* ssim;
+    double* sam_deg;
+    int64_t* sam_pixels;
+    void* workspace;
+    int64_t workspace_bytes;
+    int32_t B, C, H, W;
+} mphsir_quality_args;
+int64_t mphsir_quality_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int mphsir_quality(const mphsir_quality_args* a, void* stream);
+
 /* ---- fused AdamW over the flat parameter arena ---------------------------------------------------
  * One decoupled-weight-decay Adam step on n contiguous fp32 parameters (n % 4 == 0) with gradient g,
  * moments m, v; g is multiplied by grad_scale first (1/world_size after a sum all-reduce).
@@ -683,7 +714,8 @@ int mphsir_l1_clamp_loss(const float* y, const float* clean, float* grad, float*
 #define MPHSIR_K_SPECTRAL_DQKV_BWD 30
 #define MPHSIR_K_LAYOUT 31
 #define MPHSIR_K_SCENE 32
-#define MPHSIR_K_COUNT 33
+#define MPHSIR_K_QUALITY 33
+#define MPHSIR_K_COUNT 34
 int mphsir_prof_enable(int kid);   /* kid < 0 disables */
 int mphsir_prof_read(int* launches, float* total_ms);
 const char* mphsir_kernel_name(int kid);

@@ -145,6 +145,12 @@ class SceneBlendArgs(_Args):
                [(n, c_int32) for n in ("ny", "nx", "C", "H", "W", "th", "tw", "ov", "clamp01")]
 
 
+class QualityArgs(_Args):
+    """mirror of struct mphsir_quality_args"""
+    _fields_ = _SZ + [(n, c_void_p) for n in ("restored", "clean", "psnr", "ssim", "sam_deg", "sam_pixels", "workspace")] + \
+               [("workspace_bytes", c_int64)] + [(n, c_int32) for n in ("B", "C", "H", "W")]
+
+
 class TnProblem(ctypes.Structure):
     """mirror of struct mphsir_gemm_tn_problem"""
     _fields_ = [("A", c_void_p), ("lda", c_int64), ("B", c_void_p), ("ldb", c_int64), ("Cpart", c_void_p), ("colsum_part", c_void_p),
@@ -246,6 +252,8 @@ _SYMBOLS = {
     "mphsir_mix_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p]),
     "mphsir_scene_gather": (c_int, [ctypes.POINTER(SceneGatherArgs), c_void_p]),
     "mphsir_scene_blend": (c_int, [ctypes.POINTER(SceneBlendArgs), c_void_p]),
+    "mphsir_quality_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "mphsir_quality": (c_int, [ctypes.POINTER(QualityArgs), c_void_p]),
     "mphsir_l1_clamp_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
 }
 

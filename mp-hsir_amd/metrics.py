@@ -57,3 +57,42 @@ def compute_psnr_ssim2(restored, clean, degraded=None):
     pm = (p * use).sum(1)[ok] / n[ok]
     sm = (s * use).sum(1)[ok] / n[ok]
     return float(pm.mean()), float(sm.mean()), count
+
+
+# ---- the fused path: one HIP launch pair instead of the tensor programs above (csrc/quality.hip) --------------------------------------
+def quality_bands(restored, clean):
+    """-> (psnr (B,C), ssim (B,C), sam_deg (B,), sam_pixels (B,)) on the device: ops.quality_bands (definitions: include/mphsir.h)."""
+    from . import ops
+    return ops.quality_bands(restored, clean)
+
+
+def compute_quality(restored, clean, degraded=None):
+    """compute_psnr_ssim / compute_psnr_ssim2 through the fused kernel, plus the spectral angle: -> dict(psnr, ssim, sam, count) of
+    Python floats (count an int).  Bands are selected and images averaged as there: with `degraded`, only the bands that are entirely
+    zero in it are scored and images without one do not count (psnr = ssim = sam = 0.0 when none counts).  `sam` is the mean over
+    the images that count of the mean spectral angle in degrees, always taken over all C bands.  fp32 inputs are read as they are; one
+    device-to-host transfer, at the end."""
+    assert restored.shape == clean.shape
+    r = restored.detach()
+    c = clean.detach()
+    r = (r if r.dtype == torch.float32 else r.float()).contiguous()
+    c = (c if c.dtype == torch.float32 else c.float()).contiguous()
+    if r.dim() == 3:
+        r, c = r[None], c[None]
+    p, s, sam, _ = quality_bands(r, c)
+    if degraded is None:
+        B = r.shape[0]
+        out = torch.stack([p.mean(1).mean(), s.mean(1).mean(), sam.mean()]).tolist()
+        return dict(psnr=out[0], ssim=out[1], sam=out[2], count=B)
+    use = (degraded == 0).flatten(2).all(dim=2)                     # (B,C)
+    n = use.sum(1)
+    ok = n > 0
+    nd = n.clamp(min=1).double()
+    zero = torch.zeros((), dtype=torch.float64, device=p.device)
+    pm = torch.where(use, p, zero).sum(1) / nd                      # where, not a product: an unscored band may hold inf or NaN
+    sm = torch.where(use, s, zero).sum(1) / nd
+    cnt = ok.sum()
+    cd = cnt.clamp(min=1).double()
+    out = torch.stack([torch.where(ok, pm, zero).sum() / cd, torch.where(ok, sm, zero).sum() / cd, torch.where(ok, sam, zero).sum() / cd,
+                       cnt.double()]).tolist()
+    return dict(psnr=out[0], ssim=out[1], sam=out[2], count=int(out[3]))

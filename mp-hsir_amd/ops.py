@@ -755,6 +755,35 @@ def scene_blend_tiles(tiles, oy, ox, ov, H, W, clamp01=False, out=None):
     return out
 
 
+def quality_bands(restored, clean):
+    """restored, clean (B,C,H,W) fp32 (or (C,H,W): B = 1) -> (psnr (B,C) f64, ssim (B,C) f64, sam_deg (B,) f64, sam_pixels (B,) i64) on
+    the inputs' device: band-wise PSNR / SSIM (skimage's, data_range 1) and the mean spectral angle in degrees with the number of pixels
+    that have one, both inputs clipped to [0,1], all in float64 (the definitions: include/mphsir.h).  One launch pair on the current
+    stream, no synchronisation, no cube-sized temporary."""
+    lib = _lib.load()
+    _check(restored, clean)
+    assert restored.dtype == clean.dtype == torch.float32, "quality_bands: fp32 inputs, got %s / %s" % (restored.dtype, clean.dtype)
+    assert restored.shape == clean.shape and restored.dim() in (3, 4), "quality_bands: two (B,C,H,W) or (C,H,W) cubes of one shape, got %s / %s" \
+        % (tuple(restored.shape), tuple(clean.shape))
+    assert restored.is_contiguous() and clean.is_contiguous(), "quality_bands: contiguous inputs"
+    assert restored.device == clean.device, "quality_bands: inputs on %s and %s" % (restored.device, clean.device)
+    B, C, H, W = restored.shape if restored.dim() == 4 else (1,) + tuple(restored.shape)
+    nbytes = lib.mphsir_quality_workspace_bytes(B, C, H, W)
+    if nbytes < 0:
+        raise RuntimeError("mp-hsir_amd: quality_bands refuses (B %d, C %d, H %d, W %d): H, W >= 7, B, C <= 65535, H * W < 2^31" % (B, C, H, W))
+    dev = restored.device
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    psnr = torch.empty((B, C), dtype=torch.float64, device=dev)
+    ssim = torch.empty((B, C), dtype=torch.float64, device=dev)
+    sam = torch.empty((B,), dtype=torch.float64, device=dev)
+    npix = torch.empty((B,), dtype=torch.int64, device=dev)
+    a = _lib.QualityArgs(restored=_p(restored), clean=_p(clean), psnr=_p(psnr), ssim=_p(ssim), sam_deg=_p(sam), sam_pixels=_p(npix),
+                         workspace=_p(ws), workspace_bytes=nbytes, B=B, C=C, H=H, W=W)
+    _lib.check(lib.mphsir_quality(ctypes.byref(a), _stream(restored)), "quality")
+    _acct("quality", 0.0, 8.0 * restored.numel())
+    return psnr, ssim, sam, npix
+
+
 def round_up(n, m):
     return (n + m - 1) // m * m
 

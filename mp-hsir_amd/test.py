@@ -21,9 +21,11 @@ Test cubes: --test_dir with .mat ('data' key, as the reference) or .npy cubes; w
 Without --tile every cube is centre-cropped to multiples of 64 (crop_img, utils/image_utils.py:58-70) and restored in one forward,
 as the reference does.  With --tile N (an addition: the reference has no tiled path) cubes are NOT cropped: the degradation runs on
 the whole cube, restoration goes through scene.SceneRestorer (overlapping N x N tiles, --tile_overlap, gathered and blended on the
-GPU) and PSNR / SSIM are taken over the whole scene.  --save_restored 1 writes <output_path>/<mode label>/restored_<name>.npy
-(fp32, (C,H,W)) in either case.  The degradations are the GPU functions of degrade.py.  --ckpt_path evaluates a Lightning
-checkpoint of the reference (`net.` key prefix).
+GPU) and PSNR / SSIM are taken over the whole scene.  --quality fused scores through the fused HIP kernel (metrics.compute_quality:
+the same PSNR / SSIM in one pass over the two cubes, plus the mean spectral angle SAM in degrees, which the reference does not
+report); the default, --quality torch, is the tensor-program path and prints what it always printed.  --save_restored 1 writes
+<output_path>/<mode label>/restored_<name>.npy (fp32, (C,H,W)) in either case.  The degradations are the GPU functions of degrade.py.
+--ckpt_path evaluates a Lightning checkpoint of the reference (`net.` key prefix).
 """
 import argparse
 import os
@@ -37,7 +39,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from mp_hsir_amd import degrade as D  # noqa: E402
 from mp_hsir_amd.engine import GraphedForward  # noqa: E402
-from mp_hsir_amd.metrics import compute_psnr_ssim, compute_psnr_ssim2  # noqa: E402
+from mp_hsir_amd.metrics import compute_psnr_ssim, compute_psnr_ssim2, compute_quality  # noqa: E402
 from mp_hsir_amd.net.MP_HSIR import MP_HSIR_Net  # noqa: E402
 from mp_hsir_amd.scene import SceneRestorer  # noqa: E402
 
@@ -78,6 +80,8 @@ def build_parser():
     p.add_argument("--tile", type=int, default=0, help="0: crop to multiples of 64 and restore the cube in one forward (the reference); "
                    "N (a multiple of 64): keep the whole scene and restore it as overlapping N x N tiles")
     p.add_argument("--tile_overlap", type=int, default=32, help="nominal overlap of neighbouring tiles (at most tile // 2)")
+    p.add_argument("--quality", type=str, default="torch", choices=["torch", "fused"], help="torch: PSNR / SSIM by the tensor programs of "
+                   "metrics.py; fused: PSNR / SSIM / SAM by the fused HIP kernel (adds a sam column)")
     p.add_argument("--save_restored", type=int, default=0, help="1: write <output_path>/<mode label>/restored_<name>.npy (fp32, (C,H,W))")
     return p
 
@@ -187,6 +191,13 @@ def check_whole_scene(o, name, clean):
 
 def evaluate(o, net, dev):
     """-> (mean psnr, mean ssim, number of cubes); prints one line per cube"""
+    p, s, _, n = evaluate_quality(o, net, dev)
+    return p, s, n
+
+
+def evaluate_quality(o, net, dev):
+    """-> (mean psnr, mean ssim, mean sam in degrees or None under --quality torch, number of cubes); prints one line per cube"""
+    fused = o.quality == "fused"
     cfg_bands = net.patch_embed.proj.weight.shape[1]
     gen = torch.Generator(device=dev).manual_seed(o.seed)
     d = D.Draws(dev, o.seed + 1)
@@ -200,7 +211,7 @@ def evaluate(o, net, dev):
     out_dir = os.path.join(o.output_path, mode_dir(o))
     if o.save_restored:
         os.makedirs(out_dir, exist_ok=True)
-    ps = ss = 0.0
+    ps = ss = sa = 0.0
     n = 0
     for name, clean, real in cube_source(o, cfg_bands, dev, gen):
         if o.tile > 0:
@@ -216,13 +227,20 @@ def evaluate(o, net, dev):
         if o.save_restored:
             np.save(os.path.join(out_dir, "restored_%s.npy" % name), restored[0].float().cpu().numpy())
         clean_c = clean.clamp(0, 1)
-        if o.mode == 10:
+        if fused:
+            q = compute_quality(restored, clean_c, degraded if o.mode == 10 else None)
+            p, s, cnt = q["psnr"], q["ssim"], q["count"]
+            sa += q["sam"] * cnt
+        elif o.mode == 10:
             p, s, cnt = compute_psnr_ssim2(restored, clean_c, degraded)      # only the completed bands (test.py:523)
         else:
             p, s, cnt = compute_psnr_ssim(restored, clean_c)
         ps, ss, n = ps + p * cnt, ss + s * cnt, n + cnt
-        print("%s psnr %.2f ssim %.4f" % (name, p, s))
-    return ps / max(n, 1), ss / max(n, 1), n
+        if fused:
+            print("%s psnr %.2f ssim %.4f sam %.3f" % (name, p, s, q["sam"]))
+        else:
+            print("%s psnr %.2f ssim %.4f" % (name, p, s))
+    return ps / max(n, 1), ss / max(n, 1), (sa / max(n, 1) if fused else None), n
 
 
 def main():
@@ -240,8 +258,8 @@ def main():
     if ckpt is not None:
         net.load_state_dict({k[4:]: v for k, v in ckpt["state_dict"].items() if k.startswith("net.")}, strict=False)   # test.py:575
         print("CKPT name : {}".format(o.ckpt_path))
-    p, s, n = evaluate(o, net, dev)
-    print((MODE_LABEL[o.mode] % vars(o)) + ": psnr: %.2f, ssim: %.4f" % (p, s))
+    p, s, sam, n = evaluate_quality(o, net, dev)
+    print((MODE_LABEL[o.mode] % vars(o)) + ": psnr: %.2f, ssim: %.4f" % (p, s) + ("" if sam is None else ", sam: %.3f" % sam))
 
 
 if __name__ == "__main__":

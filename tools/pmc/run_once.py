@@ -5,7 +5,8 @@
     python tools/pmc/run_once.py tn       M N1 N2 form     token-reduction GEMM (1 transposed-read kernel, 2 ring form)
     python tools/pmc/run_once.py win      C heads H [B]    win_attn forward
     python tools/pmc/run_once.py win_bwd  C heads H [B]    win_attn backward
-    python tools/pmc/run_once.py dw                        depthwise 3x3 / wgrad / gate at the widest shapes"""
+    python tools/pmc/run_once.py dw                        depthwise 3x3 / wgrad / gate at the widest shapes
+    python tools/pmc/run_once.py quality  C H W            the fused PSNR / SSIM / SAM launch pair (fp32 cubes)"""
 import os
 import sys
 import warnings
@@ -72,6 +73,12 @@ elif kind == "dw":
         ops.dwconv3x3(x, w9)
         ops.dwconv3x3_wgrad(x, dy)
         ops.dwconv_gate(t, w9g, B, H, W)
+elif kind == "quality":
+    C, H, W = (int(v) for v in av[:3])
+    clean = torch.rand((1, C, H, W), device=dev)
+    restored = clean + torch.randn_like(clean) * 0.05
+    for _ in range(3):
+        ops.quality_bands(restored, clean)
 else:
     raise SystemExit(__doc__)
 torch.cuda.synchronize()
