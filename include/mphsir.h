@@ -588,6 +588,42 @@ typedef struct mphsir_scene_blend_args {
 } mphsir_scene_blend_args;
 int mphsir_scene_blend(const mphsir_scene_blend_args* a, void* stream);
 
+/* ---- self-ensemble over the flips and rotations of a tile (mp-hsir_amd/scene.py, ensemble = 4 / 8; the reference has no such path) ----
+ * A transform is one of the eight modes of the training augmentation (degrade.augment = the reference's data_augmentation,
+ * utils/image_utils.py:141-176): mode_m(x) = rot90 of the last two axes, counter-clockwise, m / 2 times, then an up-down flip when m is
+ * odd; inverse_m undoes it (inverse_m(mode_m(x)) == x).  Modes 2, 3, 6, 7 swap the two axes ("transposing") and need th == tw.
+ * Work is the flat, transform-major list of G * n_tiles items j = g * n_tiles + t: pass g < G, tile t < n_tiles of the plan; the mode of
+ * pass g is bits 3g .. 3g + 2 of modes_packed (by value: the host validates them).  G is 1, 2, 4 or 8; bits above 3G must be zero.
+ * mphsir_scene_gather_d4: tiles [count][C][th][tw] fp32; tiles[i] = mode_{g_j}(T_{t_j}) for i < count, j = min(j0 + i, G * n_tiles - 1)
+ *   (a batch that runs past the last item repeats it), T_t = the tile mphsir_scene_gather cuts at origins[t] (DEVICE int32 [n_tiles][2],
+ *   the same mirror map, any origin legal).  A bitwise copy.  0 <= j0 < G * n_tiles, 0 < count <= 65535, th, tw multiples of 4.
+ * mphsir_scene_fold_d4: y [count][C][th][tw] fp32 holds the restored items j0 .. j0 + count - 1 (all valid: j0 + count <= G * n_tiles);
+ *   store [n_tiles][C][th][tw] fp32.  For every tile t that has an item in the call, and every element of it:
+ *       acc = (the first of t's items in this call has g == 0) ? 0 : store[t]           (the store is not read in the first case)
+ *       acc += inverse_{g_j}(y[j - j0]) over t's items of this call in ascending j, one fp32 addition each
+ *       acc *= 1 / G   if the last of them has g == G - 1                                (exact: G is a power of two)
+ *       store[t] = acc
+ *   so that after the calls have walked all G * n_tiles items in order, in batches of any size, store[t] is the mean over the G passes
+ *   with the additions taken in ascending g -- bitwise the same for every batch size.  One thread owns an element for the whole call:
+ *   no atomics, no zero-fill launch, no temporary; tiles without an item in the call are not touched; a NaN in y stays a NaN in its
+ *   own store element.  At most 65535 tiles per call; th, tw multiples of 4; y and store 16-byte aligned and distinct.
+ * Both return MPHSIR_EINVAL for a transposing mode among the G passes when th != tw.                                              */
+typedef struct mphsir_scene_gather_d4_args {
+    uint32_t struct_size;
+    const float* scene;
+    const int32_t* origins;
+    float* tiles;
+    int32_t j0, count, n_tiles, G, modes_packed, C, H, W, th, tw;
+} mphsir_scene_gather_d4_args;
+int mphsir_scene_gather_d4(const mphsir_scene_gather_d4_args* a, void* stream);
+typedef struct mphsir_scene_fold_d4_args {
+    uint32_t struct_size;
+    const float* y;
+    float* store;
+    int32_t j0, count, n_tiles, G, modes_packed, C, th, tw;
+} mphsir_scene_fold_d4_args;
+int mphsir_scene_fold_d4(const mphsir_scene_fold_d4_args* a, void* stream);
+
 /* ---- scene quality: band-wise PSNR / SSIM and the mean spectral angle of a restored cube against the clean one, one launch pair --------
  * restored, clean: [B][C][H][W] fp32, contiguous, H >= 7, W >= 7.  Both are clipped to [0, 1] first (x < 0 ? 0 : x > 1 ? 1 : x, so a NaN
  * stays a NaN and poisons what it enters); everything after the clip is float64.

@@ -145,6 +145,17 @@ class SceneBlendArgs(_Args):
                [(n, c_int32) for n in ("ny", "nx", "C", "H", "W", "th", "tw", "ov", "clamp01")]
 
 
+class SceneGatherD4Args(_Args):
+    """mirror of struct mphsir_scene_gather_d4_args"""
+    _fields_ = _SZ + [("scene", c_void_p), ("origins", c_void_p), ("tiles", c_void_p)] + \
+               [(n, c_int32) for n in ("j0", "count", "n_tiles", "G", "modes_packed", "C", "H", "W", "th", "tw")]
+
+
+class SceneFoldD4Args(_Args):
+    """mirror of struct mphsir_scene_fold_d4_args"""
+    _fields_ = _SZ + [("y", c_void_p), ("store", c_void_p)] + [(n, c_int32) for n in ("j0", "count", "n_tiles", "G", "modes_packed", "C", "th", "tw")]
+
+
 class QualityArgs(_Args):
     """mirror of struct mphsir_quality_args"""
     _fields_ = _SZ + [(n, c_void_p) for n in ("restored", "clean", "psnr", "ssim", "sam_deg", "sam_pixels", "workspace")] + \
@@ -252,6 +263,8 @@ _SYMBOLS = {
     "mphsir_mix_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, ctypes.c_float, c_int32, c_void_p]),
     "mphsir_scene_gather": (c_int, [ctypes.POINTER(SceneGatherArgs), c_void_p]),
     "mphsir_scene_blend": (c_int, [ctypes.POINTER(SceneBlendArgs), c_void_p]),
+    "mphsir_scene_gather_d4": (c_int, [ctypes.POINTER(SceneGatherD4Args), c_void_p]),
+    "mphsir_scene_fold_d4": (c_int, [ctypes.POINTER(SceneFoldD4Args), c_void_p]),
     "mphsir_quality_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "mphsir_quality": (c_int, [ctypes.POINTER(QualityArgs), c_void_p]),
     "mphsir_l1_clamp_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),

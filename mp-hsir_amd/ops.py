@@ -755,6 +755,48 @@ def scene_blend_tiles(tiles, oy, ox, ov, H, W, clamp01=False, out=None):
     return out
 
 
+def pack_d4_modes(modes):
+    """the modes of the G passes (degrade.augment's numbering, 0..7) -> (G, modes_packed) of mphsir_scene_gather_d4 / _fold_d4"""
+    modes = [int(m) for m in modes]
+    if any(not 0 <= m <= 7 for m in modes):
+        raise ValueError("transform modes %r outside 0..7" % (modes,))
+    return len(modes), sum(m << (3 * g) for g, m in enumerate(modes))
+
+
+def scene_gather_d4(scene, origins, th, tw, j0, modes, out):
+    """scene (C,H,W) fp32, origins (n_tiles, 2) int32 on the device (the plan's, exactly one row per tile), out (count,C,th,tw) fp32: out[i] = item
+    j = min(j0 + i, G * n_tiles - 1) of the transform-major list j = g * n_tiles + t, the mirror-cut tile t under mode modes[g]
+    (degrade.augment's numbering).  n_tiles = origins.shape[0]; one launch, a bitwise copy."""
+    lib = _lib.load()
+    _check(scene, origins, out)
+    assert scene.dim() == 3 and scene.dtype == torch.float32 and scene.is_contiguous()
+    assert origins.dim() == 2 and origins.shape[1] == 2 and origins.dtype == torch.int32 and origins.is_contiguous()
+    C, H, W = scene.shape
+    G, packed = pack_d4_modes(modes)
+    assert out.dim() == 4 and out.shape[1:] == (C, th, tw) and out.dtype == torch.float32 and out.is_contiguous() and out.device == scene.device
+    a = _lib.SceneGatherD4Args(scene=_p(scene), origins=_p(origins), tiles=_p(out), j0=j0, count=out.shape[0], n_tiles=origins.shape[0], G=G,
+                               modes_packed=packed, C=C, H=H, W=W, th=th, tw=tw)
+    _lib.check(lib.mphsir_scene_gather_d4(ctypes.byref(a), _stream(scene)), "scene_gather_d4")
+    _acct("scene", 0.0, 8.0 * out.numel())
+    return out
+
+
+def scene_fold_d4(y, store, j0, count, modes):
+    """y (>= count,C,th,tw) fp32: the restored items j0 .. j0 + count - 1 (all valid); store (n_tiles,C,th,tw) fp32.  Every tile with an item
+    in the call: store[t] = (0 if its first item is pass 0 else store[t]) + the items mapped back, in ascending pass, times 1 / G once
+    the last pass is in (include/mphsir.h).  In place, one deterministic launch."""
+    lib = _lib.load()
+    _check(y, store)
+    assert y.dim() == 4 and store.dim() == 4 and y.dtype == store.dtype == torch.float32 and y.is_contiguous() and store.is_contiguous()
+    assert y.shape[1:] == store.shape[1:] and 0 < count <= y.shape[0] and y.device == store.device
+    n, C, th, tw = store.shape
+    G, packed = pack_d4_modes(modes)
+    a = _lib.SceneFoldD4Args(y=_p(y), store=_p(store), j0=j0, count=count, n_tiles=n, G=G, modes_packed=packed, C=C, th=th, tw=tw)
+    _lib.check(lib.mphsir_scene_fold_d4(ctypes.byref(a), _stream(y)), "scene_fold_d4")
+    _acct("scene", 0.0, 4.0 * count * C * th * tw + 8.0 * min(count, n) * C * th * tw)
+    return store
+
+
 def quality_bands(restored, clean):
     """restored, clean (B,C,H,W) fp32 (or (C,H,W): B = 1) -> (psnr (B,C) f64, ssim (B,C) f64, sam_deg (B,) f64, sam_pixels (B,) i64) on
     the inputs' device: band-wise PSNR / SSIM (skimage's, data_range 1) and the mean spectral angle in degrees with the number of pixels

@@ -16,11 +16,22 @@ Batching tiles is exact for this model, for a reason of its own: TVSP samples ro
 a sample's prompt map depends on the batch around it -- but when every sample of the batch carries the SAME task id all
 B rows are equal and the map is the one a batch of 1 gets.  Every other operation of the network is per sample.  So one scene is one
 task id, and a batch of mixed ids is refused.
+
+Self-ensemble (`ensemble` = 4 or 8): every tile is restored under G flip / rotation transforms, each restoration is mapped back and
+the G of them are averaged before the blend.  The transforms carry the numbers of the training augmentation -- degrade.augment, the
+reference's data_augmentation: mode m = rot90 counter-clockwise m // 2 times, then an up-down flip when m is odd -- because those
+are the eight views the weights were trained on, and the C ABI and the tests speak of the same numbers.  The network is not
+equivariant under them (shifted windows, the depthwise 3x3 taps, the prompt stretch), which is why the mean differs from one
+forward.  Work is the flat list of items j = g * n_tiles + t (pass g, tile t), walked in batches of `tile_batch` ACROSS passes:
+`mphsir_scene_gather_d4` cuts and transforms a batch in one launch, the network restores it (one task id: as exact as a batch of
+different tiles), `mphsir_scene_fold_d4` maps it back and accumulates the mean in the tile store itself (mp-hsir_amd/csrc/scene_d4.hip);
+then the same one blend.  n_tiles * G items take ceil(n_tiles * G / tile_batch) forwards; nothing cube-sized is allocated per pass.
 """
 import torch
 
 from . import ops
 
+ENSEMBLE_MODES = {1: (0,), 4: (0, 1, 4, 5), 8: (0, 1, 2, 3, 4, 5, 6, 7)}      # 4: the flips and the half turn, any tile shape; 8: needs th == tw
 GRAINS = (32, 64)       # 64: what test.py crops to; 32: the network's own limit (8-pixel windows on the coarsest of its three 2x levels)
 
 
@@ -75,17 +86,24 @@ class SceneRestorer:
     tile_batch   tiles per forward; the last batch of a scene is filled by repeating its last tile, so one shape serves them all
     graphed      an nn.Module is run through engine.GraphedForward (one capture for the one (tile_batch, C, th, tw) shape)
     grain        tile extents are multiples of it: 64 (test.py's crop granularity), or 32 (the network's own limit)
+    ensemble     1: one forward per tile.  4 / 8: the mean over the transforms ENSEMBLE_MODES[ensemble] of degrade.augment's numbering
+                 (the module docstring); 8 includes the quarter turns and needs square tiles (a ValueError at the first scene whose
+                 plan has th != tw).  tile_batch then counts (transform, tile) items, packed across passes.
 
     A tile sees the TILE's global spectral attention (the channel Gram is taken over the tile) and the tile's prompt stretch, not
     the scene's: tiled and whole-cube inference are two different functions of the input and are not expected to agree closely.
     A scene that is exactly one tile runs the same path with a batch of 1 and equals the plain forward bit for bit.
+    The ensemble averages restorations of the same tile: a tile still sees its own spectral attention, under every transform.
     """
 
-    def __init__(self, net, tile=256, overlap=32, tile_batch=4, graphed=True, grain=64):
+    def __init__(self, net, tile=256, overlap=32, tile_batch=4, graphed=True, grain=64, ensemble=1):
         plan_axis(tile, tile, overlap, grain)        # argument check only (ValueError)
         if tile_batch < 1:
             raise ValueError("tile_batch %r" % (tile_batch,))
+        if ensemble not in ENSEMBLE_MODES:
+            raise ValueError("ensemble %r: 1 (off), 4 (flips and the half turn) or 8 (all flips and rotations)" % (ensemble,))
         self.tile, self.overlap, self.tile_batch, self.grain = tile, overlap, int(tile_batch), grain
+        self.modes = ENSEMBLE_MODES[ensemble]
         if graphed and isinstance(net, torch.nn.Module):
             from .engine import GraphedForward
             net = GraphedForward(net)
@@ -101,7 +119,11 @@ class SceneRestorer:
         e = self._plans.get(key)
         if e is None:
             p = self.plan(H, W)
-            B = min(self.tile_batch, len(p))
+            G = len(self.modes)
+            if G == 8 and p.th != p.tw:
+                raise ValueError("ensemble=8 turns tiles by 90 degrees and needs square tiles; a %d x %d scene under tile %d has %d x %d "
+                                 "tiles: use ensemble=4 (the flips and the half turn)" % (H, W, self.tile, p.th, p.tw))
+            B = min(self.tile_batch, len(p) * G)
             rows = p.origins + [p.origins[-1]] * (-len(p) % B)              # the tail batch repeats the last tile
             e = self._plans[key] = (p, B, torch.tensor(rows, dtype=torch.int32, device=dev).reshape(-1, 2),
                                     torch.tensor(p.oy, dtype=torch.int32, device=dev), torch.tensor(p.ox, dtype=torch.int32, device=dev))
@@ -135,12 +157,19 @@ class SceneRestorer:
         n = len(p)
         xin, ids, store = self._static_buffers(H, W, C, s3.device, B, p)
         ids.fill_(int(task_id))
-        for k in range(0, n, B):
-            ops.scene_gather_tiles(s3, origins[k:k + B], p.th, p.tw, out=xin)
+        G = len(self.modes)
+        for k in range(0, n * G, B):               # items k .. k + B - 1 of the list j = g * n + t; ensemble 1: the tiles themselves
+            if G == 1:
+                ops.scene_gather_tiles(s3, origins[k:k + B], p.th, p.tw, out=xin)
+            else:
+                ops.scene_gather_d4(s3, origins[:n], p.th, p.tw, k, self.modes, out=xin)
             y = self.forward(xin, ids)
-            valid = min(B, n - k)
+            valid = min(B, n * G - k)
             if y.shape != xin.shape or y.dtype != torch.float32:
                 raise RuntimeError("the network returned %s %s for tiles %s" % (tuple(y.shape), y.dtype, tuple(xin.shape)))
-            store[k:k + valid].copy_(y[:valid])
+            if G == 1:
+                store[k:k + valid].copy_(y[:valid])
+            else:
+                ops.scene_fold_d4(y.contiguous(), store, k, valid, self.modes)
         out = ops.scene_blend_tiles(store, oy, ox, p.ov, H, W).reshape(scene.shape)
         return (out, store) if return_tiles else out

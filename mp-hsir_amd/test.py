@@ -23,7 +23,10 @@ as the reference does.  With --tile N (an addition: the reference has no tiled p
 the whole cube, restoration goes through scene.SceneRestorer (overlapping N x N tiles, --tile_overlap, gathered and blended on the
 GPU) and PSNR / SSIM are taken over the whole scene.  --quality fused scores through the fused HIP kernel (metrics.compute_quality:
 the same PSNR / SSIM in one pass over the two cubes, plus the mean spectral angle SAM in degrees, which the reference does not
-report); the default, --quality torch, is the tensor-program path and prints what it always printed.  --save_restored 1 writes
+report); the default, --quality torch, is the tensor-program path and prints what it always printed.  --ensemble 4 / 8 (an addition
+too) restores every tile under 4 (flips, half turn) or 8 (all flips and rotations; square tiles only) transforms of the training
+augmentation and averages the results mapped back (scene.SceneRestorer(ensemble=...)); without --tile the cropped cube is then a
+one-tile scene of that restorer, which for ensemble 1 is bitwise the plain forward.  --save_restored 1 writes
 <output_path>/<mode label>/restored_<name>.npy (fp32, (C,H,W)) in either case.  The degradations are the GPU functions of degrade.py.
 --ckpt_path evaluates a Lightning checkpoint of the reference (`net.` key prefix).
 """
@@ -82,6 +85,8 @@ def build_parser():
     p.add_argument("--tile_overlap", type=int, default=32, help="nominal overlap of neighbouring tiles (at most tile // 2)")
     p.add_argument("--quality", type=str, default="torch", choices=["torch", "fused"], help="torch: PSNR / SSIM by the tensor programs of "
                    "metrics.py; fused: PSNR / SSIM / SAM by the fused HIP kernel (adds a sam column)")
+    p.add_argument("--ensemble", type=int, default=1, choices=[1, 4, 8], help="self-ensemble: the mean over 4 (flips and the half turn) or 8 (all "
+                   "flips and rotations; needs square tiles) transformed restorations of every tile, mapped back; 1: off")
     p.add_argument("--save_restored", type=int, default=0, help="1: write <output_path>/<mode label>/restored_<name>.npy (fp32, (C,H,W))")
     return p
 
@@ -189,6 +194,23 @@ def check_whole_scene(o, name, clean):
                          "(crop the cube, or run without --tile)" % (name, H, W, o.downsample_factor))
 
 
+def scene_restorer(o, net, cache, name, H, W):
+    """the SceneRestorer of a cube: --tile's, or (--ensemble without --tile) one whose single tile is the cropped cube itself"""
+    T, ov = (o.tile, o.tile_overlap) if o.tile > 0 else (max(H, W), 0)
+    if T not in cache:
+        try:
+            cache[T] = SceneRestorer(net, tile=T, overlap=ov, ensemble=o.ensemble)   # tiles of one shape: one captured forward serves every scene
+        except ValueError as e:
+            if o.tile > 0:
+                raise SystemExit("--tile %d --tile_overlap %d: %s" % (o.tile, o.tile_overlap, e))
+            raise SystemExit("cube %s is %d x %d: --ensemble %d restores it as one %d x %d tile: %s" % (name, H, W, o.ensemble, T, T, e))
+    p = cache[T].plan(H, W)
+    if o.ensemble == 8 and p.th != p.tw:
+        raise SystemExit("cube %s is %d x %d and is restored as %d x %d tiles: --ensemble 8 turns tiles by 90 degrees and needs square ones "
+                         "(use --ensemble 4: the flips and the half turn)" % (name, H, W, p.th, p.tw))
+    return cache[T]
+
+
 def evaluate(o, net, dev):
     """-> (mean psnr, mean ssim, number of cubes); prints one line per cube"""
     p, s, _, n = evaluate_quality(o, net, dev)
@@ -201,12 +223,11 @@ def evaluate_quality(o, net, dev):
     cfg_bands = net.patch_embed.proj.weight.shape[1]
     gen = torch.Generator(device=dev).manual_seed(o.seed)
     d = D.Draws(dev, o.seed + 1)
+    scenes = o.tile > 0 or o.ensemble > 1
+    restorers = {}
     if o.tile > 0:
-        try:
-            run = SceneRestorer(net, tile=o.tile, overlap=o.tile_overlap)   # tiles of one shape: one captured forward serves every scene
-        except ValueError as e:
-            raise SystemExit("--tile %d --tile_overlap %d: %s" % (o.tile, o.tile_overlap, e))
-    else:
+        scene_restorer(o, net, restorers, "", o.tile, o.tile)      # a bad --tile / --tile_overlap ends the run before any cube is loaded
+    elif not scenes:
         run = GraphedForward(net)        # cubes of one shape: captured after two eager calls, then replayed
     out_dir = os.path.join(o.output_path, mode_dir(o))
     if o.save_restored:
@@ -220,8 +241,8 @@ def evaluate_quality(o, net, dev):
             degraded, pid = real, 1
         else:
             degraded, pid = degrade_for_mode(o, clean, d, o.model)
-        if o.tile > 0:
-            restored = run(degraded.float().contiguous(), pid)
+        if scenes:
+            restored = scene_restorer(o, net, restorers, name, *clean.shape[-2:])(degraded.float().contiguous(), pid)
         else:
             restored = run(degraded.float().contiguous(), torch.tensor([pid], device=dev))
         if o.save_restored:
