@@ -655,6 +655,89 @@ typedef struct mphsir_quality_args {
 int64_t mphsir_quality_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
 int mphsir_quality(const mphsir_quality_args* a, void* stream);
 
+/* ---- training-batch degradation: clean batch -> (degraded, clean under the same flip / rotation) in ONE launch ---------------------------
+ * The element values are those of the tensor functions of mp-hsir_amd/degrade.py (the reference's utils/degradation_utils.py:25-293 and
+ * data_augmentation, utils/image_utils.py:141-176), which stay the definition; the launch is a pure function of the clean batch, the plan
+ * below and the per-element draws: no atomics, no temporary in HBM, bitwise reproducible.  One workgroup per (sample, band) plane, staged
+ * once in LDS with a zero halo; every output pixel is computed through the inverse map of its sample's mode, so both outputs are written
+ * row-contiguously.
+ *   clean, degraded, clean_aug: [B][C][H][W] fp32, contiguous, distinct; H == W = N, N * N <= 128 * 128.
+ *   degraded = mode_aug[b](D_b(clean[b])), clean_aug = mode_aug[b](clean[b]) (a bitwise copy); mode_m as for mphsir_scene_gather_d4;
+ *   aug [B] DEVICE int32, the low three bits are used.
+ * The plan.  HOST arrays, read during the call and validated here:
+ *   menu [T <= 16]       kind (MPHSIR_DEG_*) of task id t; an unknown kind is refused
+ *   ksize [K <= 16]      side k of stencil i, odd and <= 21 (may be NULL when K == 0)
+ *   sr_factor [F <= 8]   the factors f of MPHSIR_DEG_SR: f >= 1 divides N and N / f >= 2 (may be NULL when F == 0)
+ * DEVICE tables (never validated: the kernel clamps task / sub into their ranges, so no access depends on their values); a table may be
+ * NULL when no kind of the menu reads it:
+ *   task [B] int32       task id of sample b, index into menu
+ *   param [B] fp32       GAUSSIAN: sigma; COMPLEX: impulse amount; INPAINT: ratio; HAZE: omega
+ *   sub [B] int32        COMPLEX: subtype (1 = impulse; the dead-column and offset tables of the other two come already masked);
+ *                        BLUR: stencil index < K; SR: factor index < F
+ *   band_sigma [B][C] fp32; band_flag [B][C] uint8 (COMPLEX: the bands that take impulses; BANDMISS: the lost bands);
+ *   col_dead [B][C][N] uint8, col_off [B][C][N] fp32 (COMPLEX, already masked by band and subtype);
+ *   stencils [K][21][21] fp32: stencil i in rows / columns 0 .. k_i - 1 of its slot;
+ *   cirrus [B][N][N] fp32, atm [B][C] fp32, haze_ratio [C] fp32 (HAZE).
+ * Kinds, x = the clean element, z / u0 / u1 its draws, every product and sum rounded on its own (no contraction) unless stated:
+ *   NONE      x
+ *   GAUSSIAN  x + z * sigma
+ *   COMPLEX   y = x + z * band_sigma;  y *= col_dead ? 0 : 1;  if (sub == 1 && band_flag && u0 < amount) y = u1 < 0.5 ? 1 : 0;  y - col_off
+ *   BLUR      sum over the k x k taps, rows then columns, of w[dy][dx] * x[y + dy - k/2][x + dx - k/2], zero outside the plane, one fma per tap
+ *   SR        bicubic (A = -0.75, align_corners, border-clamped taps, fp32 coordinates as F.interpolate) to N/f x N/f, each pixel f x f times
+ *   INPAINT   x * (u0 > ratio ? 1 : 0)
+ *   BANDMISS  x * (band_flag ? 0 : 1)
+ *   HAZE      t1 = 1 - omega * cirrus (<= 0 -> 1e-10), t = exp(haze_ratio[c] * log(t1)), x * t + atm * (1 - t)
+ *   A NaN therefore poisons exactly the elements whose value depends on it (a product with 0 keeps it; an impulse replaces it).
+ * Draws.  Explicit: z, u0, u1 [B][C][N][N] fp32, all three or none, read at the element's index in the UN-augmented cube.
+ * Generated (all three NULL): one Philox4x32-10 call per element (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl 0x9E3779B9 / 0xBB67AE85),
+ *   key = (low, high word of seed), counter = (low, high word of the element's linear index in the un-augmented cube, 0, low word of the
+ *   ordinal) -> r0..r3;  u0 = (r2 >> 8) 2^-24, u1 = (r3 >> 8) 2^-24 in [0, 1);  z = sqrt(-2 ln a) cos(2 pi b), a = ((r0 >> 8) + 1) 2^-24,
+ *   b = (r1 >> 8) 2^-24.  A draw depends on (seed, ordinal, element) only.  ordinal_dev (optional DEVICE int64): read by the launch
+ *   instead of `ordinal`, so that a captured launch can be replayed with another ordinal.
+ * MPHSIR_EINVAL: H != W, N * N > 128 * 128, an even or too large stencil, a factor that does not divide N or leaves N / f < 2, an
+ *   unknown kind, one or two of z / u0 / u1, a table missing that a kind of the menu reads, B * C >= 2^31.  Element indices are 64-bit.
+ *   LDS: the plane with the largest halo of the stencil table, plus the low-resolution image when the menu has SR: 86 + 16 KiB at most.  */
+#define MPHSIR_DEG_NONE 0
+#define MPHSIR_DEG_GAUSSIAN 1
+#define MPHSIR_DEG_COMPLEX 2
+#define MPHSIR_DEG_BLUR 3
+#define MPHSIR_DEG_SR 4
+#define MPHSIR_DEG_INPAINT 5
+#define MPHSIR_DEG_BANDMISS 6
+#define MPHSIR_DEG_HAZE 7
+#define MPHSIR_DEG_MAX_TASKS 16
+#define MPHSIR_DEG_MAX_STENCILS 16
+#define MPHSIR_DEG_MAX_FACTORS 8
+#define MPHSIR_DEG_STENCIL_SIDE 21
+typedef struct mphsir_degrade_args {
+    uint32_t struct_size;       /* = sizeof(this struct), set by the caller: any other value is rejected with MPHSIR_EINVAL */
+    const float* clean;
+    float* degraded;
+    float* clean_aug;
+    const int32_t* menu;
+    const int32_t* ksize;
+    const int32_t* sr_factor;
+    const int32_t* task;
+    const int32_t* aug;
+    const float* param;
+    const int32_t* sub;
+    const float* band_sigma;
+    const uint8_t* band_flag;
+    const uint8_t* col_dead;
+    const float* col_off;
+    const float* stencils;
+    const float* cirrus;
+    const float* atm;
+    const float* haze_ratio;
+    const float* z;
+    const float* u0;
+    const float* u1;
+    const int64_t* ordinal_dev;
+    int64_t seed, ordinal;
+    int32_t B, C, H, W, T, K, F;
+} mphsir_degrade_args;
+int mphsir_degrade_batch(const mphsir_degrade_args* a, void* stream);
+
 /* ---- fused AdamW over the flat parameter arena ---------------------------------------------------
  * One decoupled-weight-decay Adam step on n contiguous fp32 parameters (n % 4 == 0) with gradient g,
  * moments m, v; g is multiplied by grad_scale first (1/world_size after a sum all-reduce).
@@ -751,7 +834,8 @@ int mphsir_l1_clamp_loss(const float* y, const float* clean, float* grad, float*
 #define MPHSIR_K_LAYOUT 31
 #define MPHSIR_K_SCENE 32
 #define MPHSIR_K_QUALITY 33
-#define MPHSIR_K_COUNT 34
+#define MPHSIR_K_DEGRADE 34
+#define MPHSIR_K_COUNT 35
 int mphsir_prof_enable(int kid);   /* kid < 0 disables */
 int mphsir_prof_read(int* launches, float* total_ms);
 const char* mphsir_kernel_name(int kid);

@@ -162,6 +162,14 @@ class QualityArgs(_Args):
                [("workspace_bytes", c_int64)] + [(n, c_int32) for n in ("B", "C", "H", "W")]
 
 
+class DegradeArgs(_Args):
+    """mirror of struct mphsir_degrade_args"""
+    _fields_ = _SZ + [(n, c_void_p) for n in ("clean", "degraded", "clean_aug", "menu", "ksize", "sr_factor", "task", "aug", "param", "sub", "band_sigma",
+                                         "band_flag", "col_dead", "col_off", "stencils", "cirrus", "atm", "haze_ratio", "z", "u0", "u1",
+                                         "ordinal_dev")] + [("seed", c_int64), ("ordinal", c_int64)] + \
+               [(n, c_int32) for n in ("B", "C", "H", "W", "T", "K", "F")]
+
+
 class TnProblem(ctypes.Structure):
     """mirror of struct mphsir_gemm_tn_problem"""
     _fields_ = [("A", c_void_p), ("lda", c_int64), ("B", c_void_p), ("ldb", c_int64), ("Cpart", c_void_p), ("colsum_part", c_void_p),
@@ -267,6 +275,7 @@ _SYMBOLS = {
     "mphsir_scene_fold_d4": (c_int, [ctypes.POINTER(SceneFoldD4Args), c_void_p]),
     "mphsir_quality_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "mphsir_quality": (c_int, [ctypes.POINTER(QualityArgs), c_void_p]),
+    "mphsir_degrade_batch": (c_int, [ctypes.POINTER(DegradeArgs), c_void_p]),
     "mphsir_l1_clamp_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
 }
 

@@ -22,14 +22,15 @@ class SyntheticPatchSource:
     degrade.DegradationSynthesizer, task id = index of the degradation applied (as ImageTransformDataset does)."""
 
     def __init__(self, bands=31, patch=64, batch=32, task_classes=6, device="cuda", seed=2024, rank=0, de_types=None,
-                 data_type="natural_scene", pool=0):
+                 data_type="natural_scene", pool=0, fused_degrade=False):
         # pool = n > 0: the first n batches are generated once and handed out round-robin afterwards -- the inputs of a timed run are
         # then resident in HBM before the timed region starts (the reference's loader workers run beside the GPU, not on it)
         self.pool, self._pooled, self._turn = pool, [], 0
         self.shape = (batch, bands, patch, patch)
         self.task_classes, self.device = task_classes, device
         self.gen = torch.Generator(device=device).manual_seed(seed + 7919 * rank)
-        self.syn = degrade.DegradationSynthesizer(data_type, de_types, device, seed + 7919 * rank + 1) if de_types else None
+        # fused_degrade: the synthesiser's one-launch path (degrade.DegradationSynthesizer(fused=True)); off = the tensor programs
+        self.syn = degrade.DegradationSynthesizer(data_type, de_types, device, seed + 7919 * rank + 1, fused=fused_degrade) if de_types else None
 
     def next(self):
         if self.pool:
@@ -120,11 +121,11 @@ class PatchDBSource:
     (dataset_utils.py:131-132), and degrade.DegradationSynthesizer produces (degraded, clean, prompt) on the device.
     Each rank walks its own seeded permutation (DistributedSampler-style shard: index = perm[rank::world])."""
 
-    def __init__(self, db, batch, de_types, data_type, device, seed=2024, rank=0, world=1, repeat=1):
+    def __init__(self, db, batch, de_types, data_type, device, seed=2024, rank=0, world=1, repeat=1, fused_degrade=False):
         self.db, self.batch, self.device, self.data_type = db, batch, torch.device(device), data_type
         self.rank, self.world, self.repeat = rank, world, repeat
         self.rng = np.random.RandomState(seed)                       # same permutation on every rank, then sharded
-        self.syn = degrade.DegradationSynthesizer(data_type, de_types, device, seed + 7919 * rank + 1)
+        self.syn = degrade.DegradationSynthesizer(data_type, de_types, device, seed + 7919 * rank + 1, fused=fused_degrade)
         self.order, self.pos, self._copied = None, 0, None
         c, h, w = db.records[0][1]
         self.stage = torch.empty((batch, c, h, w), dtype=torch.float32)

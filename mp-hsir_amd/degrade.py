@@ -13,7 +13,9 @@ same numpy calls to recover the draws they consumed, and stores (draws, output);
 (oracle/degrade_oracle.py) and these functions must reproduce the outputs from the draws (tests/test_degrade.py).
 
 All functions take and return (B,C,H,W) float32 cubes; per-sample draws carry a leading batch axis.  PyTorch device ops
-only (this is the loader side of the boundary, not the model hot path).  `file:line` = reference repository.
+only (this is the loader side of the boundary, not the model hot path) -- except DegradationSynthesizer(fused=True), which builds a
+plan of small tables with batched tensor ops, without a host synchronisation, and degrades the batch in ONE HIP launch
+(csrc/degrade.hip, ops.degrade_batch); the functions here stay the definition of every element value.  `file:line` = reference repository.
 """
 import math
 
@@ -255,13 +257,16 @@ class DegradationSynthesizer:
     applied to both cubes; emits `degrad_patch, clean_patch, prompt (B,1) int64`.  `cirrus` (a callable (B,H,W) -> maps in
     [0,1]) supplies the haze maps the reference reads from .mat files (:245-257); default: smooth synthetic fields."""
 
-    def __init__(self, data_type, de_types, device, seed=2024, cirrus=None):
+    def __init__(self, data_type, de_types, device, seed=2024, cirrus=None, fused=False):
         self.table, self.de_types = DE_DICT[data_type], list(de_types)
         for t in self.de_types:
             if t not in self.table:
                 raise ValueError("degradation %r is not defined for %s" % (t, data_type))
         self.d = Draws(device, seed)
         self.cirrus = cirrus or self._synthetic_cirrus
+        self.fused = bool(fused)
+        if self.fused:
+            self._init_fused(seed)
 
     def _synthetic_cirrus(self, B, H, W):
         low = self.d.rand(B, 1, max(H // 16, 2), max(W // 16, 2))
@@ -305,8 +310,111 @@ class DegradationSynthesizer:
             return poisson_noise(x, float(rng[0][0]), generator=d.gen)
         raise ValueError("Invalid degradation type " + de_type)
 
+    # ---- fused=True: a plan of small device tables (batched tensor ops, no host synchronisation) + ONE launch (csrc/degrade.hip) ----
+    def _init_fused(self, seed):
+        """everything that would otherwise be a host -> device copy inside the call: the value lists of DE_DICT as device tensors, the
+        stencil table, the batch ordinal (a device scalar the launch reads: a captured call advances it by itself)."""
+        from . import ops
+        if "poissonN" in self.de_types:
+            raise ValueError("poissonN has no fused form (its parity is distribution-level only): use fused=False for a menu with poissonN")
+        dev = self.d.device
+        self.seed = int(seed)
+        self._menu = [ops.DEG_KINDS[t] for t in self.de_types]
+        self._vals, self._st_base, kernels = {}, {}, []
+        for name in self.de_types:
+            rng = self.table[name]
+            if name in ("blur", "circle_blur", "motion_blur"):
+                self._st_base[name] = len(kernels)
+                kernels += [gaussian_kernel2d(k) if name == "blur" else circle_kernel2d(k) if name == "circle_blur" else motion_kernel2d(*k)
+                            for k in rng[0]]
+            elif name == "complexN":
+                self._vals["complexN/sigma"] = torch.tensor([v / 255.0 for v in rng[0]], dtype=torch.float32, device=dev)
+                self._vals["complexN/amount"] = torch.tensor(list(rng[2]), dtype=torch.float32, device=dev)
+            elif name in ("inpaint", "bandmiss", "haze"):
+                self._vals[name] = torch.tensor(list(rng[0]), dtype=torch.float32, device=dev)
+        self._ksize = [int(k.shape[-1]) for k in kernels]
+        self._stencils = None
+        if kernels:
+            st = torch.zeros((len(kernels), 21, 21), dtype=torch.float32)
+            for i, k in enumerate(kernels):
+                st[i, :k.shape[0], :k.shape[1]] = k
+            self._stencils = st.to(dev)
+        self._factors = [int(f) for f in self.table["sr"][0]] if "sr" in self.de_types else []
+        self._haze_ratio = {}
+        self._ordinal = torch.full((1,), -1, dtype=torch.int64, device=dev)
+
+    def _pick(self, key, n):
+        v = self._vals[key]
+        return v[self.d.randint(0, v.shape[0], (n,))]
+
+    def fused_plan(self, clean):
+        """-> (ops.DegradePlan, de_id (B,)): the draws `degrade_as` makes per type, made for the whole batch with batched tensor ops and
+        merged by task id with torch.where -- no nonzero / item / boolean indexing, so nothing waits for the device."""
+        from . import ops
+        d = self.d
+        B, C, H, W = clean.shape
+        dev = clean.device
+        de_id = d.randint(0, len(self.de_types), (B,))
+        param = torch.zeros((B,), dtype=torch.float32, device=dev)
+        sub = torch.zeros((B,), dtype=torch.int64, device=dev)
+        tabs, flag = {}, None
+        for t, name in enumerate(self.de_types):
+            rng, mine = self.table[name], de_id == t
+            if name == "gaussianN":
+                lo, hi = rng[0]
+                param = torch.where(mine, (lo + (hi - lo) * d.rand(B)) / 255.0, param)
+            elif name == "complexN":
+                _, deadline, _, stripe = rng
+                tabs["band_sigma"] = self._pick("complexN/sigma", B * C).reshape(B, C).contiguous()
+                kind = d.randint(0, 3, (B,))
+                bands = d.band_subset(B, C, int(math.floor(C / 3)))
+                nd = d.randint(math.ceil(deadline[0] * W), max(math.ceil(deadline[1] * W), math.ceil(deadline[0] * W) + 1), (B, C))
+                dead = d.column_subsets(B, C, W, nd) & bands[:, :, None] & (kind == 0).reshape(B, 1, 1)
+                ns = d.randint(math.floor(stripe[0] * W), max(math.floor(stripe[1] * W), math.floor(stripe[0] * W) + 1), (B, C))
+                cols = d.column_subsets(B, C, W, ns) & bands[:, :, None] & (kind == 2).reshape(B, 1, 1)
+                tabs["col_dead"] = dead.to(torch.uint8)
+                tabs["col_off"] = (d.rand(B, C, W) * 0.5 - 0.25) * cols
+                param = torch.where(mine, self._pick("complexN/amount", B), param)
+                sub = torch.where(mine, kind, sub)
+                flag = bands if flag is None else torch.where(mine[:, None], bands, flag)
+            elif name in ("blur", "circle_blur", "motion_blur"):
+                sub = torch.where(mine, self._st_base[name] + d.randint(0, len(rng[0]), (B,)), sub)
+            elif name == "sr":
+                sub = torch.where(mine, d.randint(0, len(rng[0]), (B,)), sub)
+            elif name == "inpaint":
+                param = torch.where(mine, self._pick("inpaint", B), param)
+            elif name == "bandmiss":
+                n = (self._pick("bandmiss", B) * C).long()                              # int(loss_percentage * B)
+                lost = d.rand(B, C).argsort(dim=1).argsort(dim=1) < n[:, None]
+                flag = lost if flag is None else torch.where(mine[:, None], lost, flag)
+            elif name == "haze":
+                param = torch.where(mine, self._pick("haze", B), param)
+                tabs["cirrus"] = self.cirrus(B, H, W).to(torch.float32).contiguous()
+                top_k = max(int(H * W * 0.01 / 100), 1)
+                flat = clean.reshape(B, C, -1)
+                tabs["atm"] = flat.amax(dim=-1) if top_k == 1 else flat.topk(top_k, dim=-1).values.mean(-1)
+                if C not in self._haze_ratio:
+                    lam = torch.linspace(400, 1000, 100, device=dev, dtype=torch.float64)[:C]
+                    self._haze_ratio[C] = (lam[0] / lam).to(torch.float32)
+                tabs["haze_ratio"] = self._haze_ratio[C]
+        if flag is not None:
+            tabs["band_flag"] = flag.to(torch.uint8)
+        plan = ops.DegradePlan(self._menu, self._ksize, self._factors, task=de_id.to(torch.int32), aug=d.randint(1, 8, (B,)).to(torch.int32),
+                               param=param, sub=sub.to(torch.int32), stencils=self._stencils, **tabs)
+        return plan, de_id
+
+    def _call_fused(self, clean):
+        from . import ops
+        clean = clean.contiguous()
+        plan, de_id = self.fused_plan(clean)
+        self._ordinal += 1                                                               # the batch ordinal counts calls, on the device
+        degraded, clean_aug = ops.degrade_batch(clean, plan, seed=self.seed, ordinal=self._ordinal)
+        return degraded, clean_aug, de_id.reshape(-1, 1)
+
     def __call__(self, clean):
         """clean (B,C,H,W) on the device -> (degraded, clean_augmented, prompt (B,1) int64)"""
+        if self.fused:
+            return self._call_fused(clean)
         B = clean.shape[0]
         de_id = self.d.randint(0, len(self.de_types), (B,))
         degraded = torch.empty_like(clean)

@@ -826,6 +826,64 @@ def quality_bands(restored, clean):
     return psnr, ssim, sam, npix
 
 
+DEG_KINDS = {"none": 0, "gaussianN": 1, "complexN": 2, "blur": 3, "motion_blur": 3, "circle_blur": 3, "sr": 4, "inpaint": 5, "bandmiss": 6,
+             "haze": 7}             # MPHSIR_DEG_* of include/mphsir.h (every blur is a stencil); poissonN has no fused form
+_DEG_TABLES = (("task", torch.int32, "b"), ("aug", torch.int32, "b"), ("param", torch.float32, "b"), ("sub", torch.int32, "b"),
+               ("band_sigma", torch.float32, "bc"), ("band_flag", torch.uint8, "bc"), ("col_dead", torch.uint8, "bcn"),
+               ("col_off", torch.float32, "bcn"), ("stencils", torch.float32, "k"), ("cirrus", torch.float32, "bnn"),
+               ("atm", torch.float32, "bc"), ("haze_ratio", torch.float32, "c"))
+
+
+class DegradePlan:
+    """The plan of mphsir_degrade_batch (include/mphsir.h): three short host lists -- `menu` (the kind code of every task id), `ksize`
+    (the side of every stencil), `sr_factor` -- and the device tables named in _DEG_TABLES, None where no kind of the menu reads one."""
+
+    def __init__(self, menu, ksize=(), sr_factor=(), **tables):
+        self.menu, self.ksize, self.sr_factor = [int(v) for v in menu], [int(v) for v in ksize], [int(v) for v in sr_factor]
+        for name, _, _ in _DEG_TABLES:
+            setattr(self, name, tables.pop(name, None))
+        if tables:
+            raise TypeError("DegradePlan: unknown tables %s" % sorted(tables))
+
+
+def degrade_batch(clean, plan, *, seed, ordinal, draws=None, out=None):
+    """clean (B,C,N,N) fp32, plan: a DegradePlan -> (degraded, clean_aug), each sample degraded by the kind of its task and both cubes under
+    its flip / rotation plan.aug (degrade.augment's modes), in ONE launch on the current stream.  draws = (z, u0, u1), three (B,C,N,N)
+    fp32 cubes read at the un-augmented element, or None: Philox4x32-10 draws from (seed, ordinal, element).  ordinal: an int, or a
+    one-element int64 tensor on the device that the launch itself reads (a captured launch replays with whatever it holds then).
+    out = (degraded, clean_aug) to write into."""
+    lib = _lib.load()
+    tabs = [getattr(plan, n) for n, _, _ in _DEG_TABLES]
+    dr = tuple(draws) if draws is not None else (None, None, None)
+    od = ordinal if torch.is_tensor(ordinal) else None
+    _check(clean, od, *tabs, *dr, *(out or ()))
+    assert clean.dim() == 4 and clean.dtype == torch.float32 and clean.is_contiguous(), "degrade_batch: a contiguous (B,C,N,N) fp32 batch"
+    B, C, H, W = clean.shape
+    want = {"b": (B,), "bc": (B, C), "bcn": (B, C, W), "k": (len(plan.ksize), 21, 21), "bnn": (B, H, W), "c": (C,)}
+    for (name, dt, shp), t in zip(_DEG_TABLES, tabs):
+        assert t is None or (t.dtype == dt and tuple(t.shape) == want[shp] and t.is_contiguous() and t.device == clean.device), \
+            "degrade_batch: plan.%s must be a contiguous %s tensor of shape %s on %s" % (name, dt, want[shp], clean.device)
+    for t in dr:
+        assert t is None or (t.dtype == torch.float32 and t.shape == clean.shape and t.is_contiguous() and t.device == clean.device), \
+            "degrade_batch: explicit draws are contiguous fp32 cubes of the batch's shape"
+    if od is not None:
+        assert od.dtype == torch.int64 and od.numel() == 1 and od.device == clean.device, "degrade_batch: a device ordinal is one int64"
+    if out is None:
+        out = (torch.empty_like(clean), torch.empty_like(clean))
+    for t in out:
+        assert t.shape == clean.shape and t.dtype == torch.float32 and t.is_contiguous() and t.device == clean.device
+    assert out[0].data_ptr() != out[1].data_ptr() and clean.data_ptr() not in (out[0].data_ptr(), out[1].data_ptr()), "degrade_batch: distinct cubes"
+    host = [(ctypes.c_int32 * max(len(v), 1))(*v) for v in (plan.menu, plan.ksize, plan.sr_factor)]
+    a = _lib.DegradeArgs(clean=_p(clean), degraded=_p(out[0]), clean_aug=_p(out[1]), menu=ctypes.addressof(host[0]),
+                         ksize=ctypes.addressof(host[1]) if plan.ksize else None, sr_factor=ctypes.addressof(host[2]) if plan.sr_factor else None,
+                         z=_p(dr[0]), u0=_p(dr[1]), u1=_p(dr[2]), ordinal_dev=_p(od), seed=ctypes.c_int64(int(seed) & 0xFFFFFFFFFFFFFFFF).value,
+                         ordinal=0 if od is not None else int(ordinal), B=B, C=C, H=H, W=W, T=len(plan.menu), K=len(plan.ksize),
+                         F=len(plan.sr_factor), **{n: _p(t) for (n, _, _), t in zip(_DEG_TABLES, tabs)})
+    _lib.check(lib.mphsir_degrade_batch(ctypes.byref(a), _stream(clean)), "degrade_batch")
+    _acct("degrade", 0.0, 12.0 * clean.numel())
+    return out
+
+
 def round_up(n, m):
     return (n + m - 1) // m * m
 

@@ -118,14 +118,14 @@ def main():
     de_types = opt.natural_scene_single_de_type if data_type == "natural_scene" else opt.remote_sensing_single_de_type
     if opt.synthetic:
         src = SyntheticPatchSource(cfg["in_channel"], opt.patch_size, opt.batch_size, cfg["task_classes"], dev, opt.seed, rank,
-                                   de_types=de_types, data_type=data_type)
+                                   de_types=de_types, data_type=data_type, fused_degrade=bool(opt.fused_degrade))
         steps_per_epoch = opt.steps_per_epoch
     else:
         if not opt.db_path:
             raise SystemExit("--synthetic 0 needs --db_path <directory with data.bin + meta_info.txt> (data.write_patch_db)")
         keep_all = data_type == "natural_scene" or opt.all_sources          # dataset_utils.py:56 filters remote-sensing sources
         db = PatchDB(opt.db_path, dataset_names=None if keep_all else REMOTE_SENSING_SOURCES)
-        src = PatchDBSource(db, opt.batch_size, de_types, data_type, dev, opt.seed, rank, world, opt.repeat)
+        src = PatchDBSource(db, opt.batch_size, de_types, data_type, dev, opt.seed, rank, world, opt.repeat, fused_degrade=bool(opt.fused_degrade))
         steps_per_epoch = src.steps_per_epoch()
     for epoch in range(start_epoch, opt.epochs):
         lr = warmup_cosine_lr(epoch, opt.lr, opt.epochs)
