@@ -117,8 +117,7 @@ class FoldBwdArgs(_Args):
     """mirror of struct mphsir_fold_bwd_args"""
     _fields_ = _SZ + [(n, c_void_p) for n in ("Gpart", "Spart", "temperature", "Wo", "dM", "W2", "dWo", "dtemp")] + \
                [(n, c_int32) for n in ("B", "C", "heads", "nsplit", "dM_nsplit")] + \
-               [("DO", c_void_p), ("lddo", c_int64), ("V", c_void_p), ("ldv", c_int64), ("N", c_int32), ("dm_scale", c_void_p),
-                ("w2_blocks", c_int32)]
+               [("DO", c_void_p), ("lddo", c_int64), ("V", c_void_p), ("ldv", c_int64), ("N", c_int32), ("w2_blocks", c_int32)]
 
 
 class PgBwdArgs(_Args):
@@ -131,7 +130,7 @@ class SpectralBwdArgs(_Args):
     """mirror of struct mphsir_spectral_bwd_args"""
     _fields_ = _SZ + [("QK", c_void_p), ("ldqk", c_int64), ("DO", c_void_p), ("lddo", c_int64), ("T", c_void_p), ("ldt", c_int64),
                       ("W2", c_void_p), ("MbT", c_void_p), ("w9", c_void_p), ("ldw", c_int64), ("dT", c_void_p), ("lddt", c_int64),
-                      ("part", c_void_p)] + [(n, c_int32) for n in ("B", "H", "W", "C", "heads", "nblk", "round_dall")] + [("vscale", c_void_p)]
+                      ("part", c_void_p)] + [(n, c_int32) for n in ("B", "H", "W", "C", "heads", "nblk", "round_dall")]
 
 
 class SceneGatherArgs(_Args):
@@ -220,8 +219,6 @@ _SYMBOLS = {
     "mphsir_dwconv_gate": (c_int, [ctypes.POINTER(GateArgs), c_int, c_void_p]),
     "mphsir_dwconv_gate_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int, c_void_p]),
     "mphsir_dwconv_gate_bwd_fits": (c_int, [c_int32, c_int32, c_int32, c_int]),
-    "mphsir_gdfn_dw_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int, c_void_p]),
-    "mphsir_gdfn_dw_bwd_fits": (c_int, [c_int32, c_int32, c_int32, c_int]),
     "mphsir_gdfn_fused": (c_int, [ctypes.POINTER(GdfnArgs), c_int, c_void_p]),
     "mphsir_gdfn_fused_fits": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int]),
     "mphsir_gdfn_fused_tile_width": (c_int, [c_int32]),

@@ -143,11 +143,7 @@ class reduce_scope:
             elif self.leaf and _DEFERRED is not None:
                 _flush_calls(self.calls)
                 _flush_gemms(self.gemms)
-                # ... their sums later, with everybody else's.  The output is kept alive through a detached alias: the tensor
-                # object itself must stay uniquely referenced so that AccumulateGrad adopts it instead of cloning (= reading) it
-                for g in self.segs:
-                    g["keep"] = (g["keep"][0], g["keep"][1].detach())
-                _poison(self.segs)
+                _hand_out(self.segs)            # ... their sums later, with everybody else's
                 _DEFERRED.extend(self.segs)
             else:
                 _flush_calls(self.calls)
@@ -164,8 +160,17 @@ class reduce_scope:
 # the CUs the small launches of the lower pyramid levels leave idle, reading the partials while they are still in the Infinity
 # Cache.  Every tensor involved stays referenced until the join (nothing is recycled under the branch).
 DW_SIDE = int(os.environ.get("MPHSIR_DW_SIDE", "2"))
-_DW_STREAM = {}
-_DW_KEEP = []
+DW_BATCH_BYTES = int(float(os.environ.get("MPHSIR_DW_BATCH_MB", "256")) * (1 << 20))      # 0 / 24 / 48 / 128 / 256 / 512 MB: 20.90 / 20.82 / 20.75 / 20.67 / 20.60 / 20.63 ms per step (one box, pairs)
+_DW = {}      # device -> its _DwBranch
+
+
+class _DwBranch:
+    """the weight-gradient branch of one device: its stream, the batch that waits for its flush (DW_SIDE = 2) and `keep`, every
+    tensor that work issued on the branch reads or writes (released by the final join)"""
+
+    def __init__(self, dev):
+        self.stream = torch.cuda.Stream(dev)
+        self.gemms, self.calls, self.segs, self.nbytes, self.keep = [], [], [], 0, []
 
 
 # MPHSIR_DEBUG_DEFERRED=1 (tests): every parameter-gradient sum that is handed out before it has been computed (deferred to the end
@@ -175,10 +180,21 @@ _DW_KEEP = []
 DEBUG_DEFERRED = os.environ.get("MPHSIR_DEBUG_DEFERRED", "0") == "1"
 
 
-def _poison(segs):
+def _hand_out(segs):
+    """the outputs of `segs` leave their backward function before they are computed: each is kept alive through a detached alias --
+    the tensor object itself must stay uniquely referenced so that AccumulateGrad adopts it instead of cloning (= reading) it"""
+    for g in segs:
+        g["keep"] = (g["keep"][0], g["keep"][1].detach())
     if DEBUG_DEFERRED:
         for g in segs:
             g["keep"][1].fill_(float("nan"))
+
+
+def _wait_side_streams(st, dev):
+    """`st` waits for every (tracked) side stream this backward pass has forked on `dev`"""
+    for d2, s2 in list(_SIDE_USED):
+        if d2 == dev and s2 != st:
+            st.wait_stream(s2)
 
 
 def _dw_side(scope):
@@ -189,124 +205,65 @@ def _dw_side(scope):
     if like is None or not like.is_cuda:
         return False
     dev = like.device
-    st = _DW_STREAM.get(dev)
-    if st is None:
-        st = _DW_STREAM[dev] = torch.cuda.Stream(dev)
-    main = torch.cuda.current_stream(dev)
-    for g in scope.segs:                # AccumulateGrad must find the output uniquely referenced: keep a detached alias
-        g["keep"] = (g["keep"][0], g["keep"][1].detach())
-    _poison(scope.segs)
+    br = _DW.get(dev)
+    if br is None:
+        br = _DW[dev] = _DwBranch(dev)
+    _hand_out(scope.segs)
     if DW_SIDE >= 2:
         # Small backward functions (the lower pyramid levels: a few MB of operands, launches that cost their 15-30 us floor whatever
         # they move) are BATCHED: their problems wait until DW_BATCH_BYTES of operands, a full grouped launch (8 problems) or 32 sum
         # segments have come together, and go out as ONE grouped GEMM launch + ONE ordered-sum launch; a big function flushes at once
-        # (with whatever is pending, in issue order).  The operands stay referenced (pending list, then _DW_KEEP).
-        nbytes = sum(g["M"] * (g["N1"] + g["N2"]) * 2 for g in scope.gemms)
-        rows = max([g["M"] for g in scope.gemms] + [c["keep"][0].shape[0] for c in scope.calls if c["keep"][0].dim() == 2] + [0])
-        if DW_DEFER and rows >= DW_DEFER_ROWS:
-            # a BIG backward function (the full-resolution level: 131072 token rows at batch 32): its weight-gradient work is HELD, not
-            # issued -- beside the equally big data-gradient kernels of the next block it only shares the CUs and HBM with them.  It goes
-            # out when the backward pass reaches the lower pyramid levels (below), whose launches are latency-bound and leave most of the
-            # chip idle: the branch then fills that idle time.  What the last big functions of a pass hold (encoder level 1) is issued
-            # by the join.  Operands stay referenced (held list, then _DW_KEEP).
-            _DW_HELD.setdefault(dev, []).append((scope.gemms, scope.calls, scope.segs))
-            return True
-        if DW_DEFER and rows > 0:
-            _dw_release_held(dev)           # a small function: the held work of the big ones starts now, ahead of this function's own
-        pend = _DW_PENDING.setdefault(dev, [[], [], [], 0])
-        pend[0] += scope.gemms
-        pend[1] += scope.calls
-        pend[2] += scope.segs
-        pend[3] += nbytes
-        if scope.calls or pend[3] >= DW_BATCH_BYTES or len(pend[0]) + 3 > _lib.TN_GROUP_MAX or len(pend[2]) + 17 > _lib.REDUCE_MAX_SEGS:
+        # (with whatever is pending, in issue order).  The operands stay referenced (the batch, then `keep`).
+        br.gemms += scope.gemms
+        br.calls += scope.calls
+        br.segs += scope.segs
+        br.nbytes += sum(g["M"] * (g["N1"] + g["N2"]) * 2 for g in scope.gemms)
+        if scope.calls or br.nbytes >= DW_BATCH_BYTES or len(br.gemms) + 3 > _lib.TN_GROUP_MAX or len(br.segs) + 17 > _lib.REDUCE_MAX_SEGS:
             _dw_flush_pending(dev)
-        return True
-    else:
+    else:                                   # the GEMMs stay on the launch stream: only their sums fork
         _flush_calls(scope.calls)
         _flush_gemms(scope.gemms)
-        st.wait_stream(main)
-        for d2, s2 in list(_SIDE_USED):      # (as in _dw_flush_pending)
-            if d2 == dev and s2 != st:
-                st.wait_stream(s2)
-        with torch.cuda.stream(st):
-            _flush(scope.segs)
-    _DW_KEEP.append((dev, [g["keep"] for g in scope.gemms] + [c["keep"] for c in scope.calls], [g["keep"] for g in scope.segs]))
+        br.keep += [g["keep"] for g in scope.gemms + scope.calls]
+        _dw_fork(dev, [], [], scope.segs)
     return True
 
 
-DW_BATCH_BYTES = int(float(os.environ.get("MPHSIR_DW_BATCH_MB", "256")) * (1 << 20))      # 0 / 24 / 48 / 128 / 256 / 512 MB: 20.90 / 20.82 / 20.75 / 20.67 / 20.60 / 20.63 ms per step (one box, pairs)
-_DW_PENDING = {}
-# MPHSIR_DW_DEFER=1 (round-6 experiment, OFF): the weight-gradient work of the big (full-resolution) backward functions is held back until
-# the pass reaches the lower pyramid levels, whose latency-bound launches leave most of the chip idle.  Measured SLOWER (20.31-20.35
-# against 20.07-20.09 ms per step, two pairs on one box; with the 32768-row level held too: 20.45-20.50): beside a grouped GEMM that
-# fills every CU the small launches of the main chain wait for workgroup slots -- the chain loses more than the branch hides.
-DW_DEFER = os.environ.get("MPHSIR_DW_DEFER", "0") == "1"
-DW_DEFER_ROWS = int(os.environ.get("MPHSIR_DW_DEFER_ROWS", "65536"))
-_DW_HELD = {}
-# the ordered sums of the weight-gradient branch: 1 = all of them at the join (the end of the backward pass / a bucket hook), as few
-# launches of 32 segments as there can be, instead of one small launch behind every flush of the branch
-DW_SUMS_LATE = os.environ.get("MPHSIR_DW_SUMS_LATE", "0") == "1"
-_DW_SUMS = {}
-
-
-def _dw_release_held(dev):
-    """issue the held weight-gradient work of the big backward functions on the branch: function by function in the order they ran
-    (a grouped GEMM launch + an ordered-sum launch each time DW_BATCH_BYTES of operands have come together)"""
-    held = _DW_HELD.get(dev)
-    if not held:
-        return
-    _dw_flush_pending(dev)                  # what was pending before goes first
-    _DW_HELD[dev] = []
-    for gemms, calls, segs in held:         # one batch per function: its sums follow its GEMMs while the partials are on the die
-        _DW_PENDING[dev] = [list(gemms), list(calls), list(segs), 0]
-        _dw_flush_pending(dev)
+def _dw_fork(dev, gemms, calls, segs):
+    br = _DW[dev]
+    br.stream.wait_stream(torch.cuda.current_stream(dev))
+    # a batch may hold problems whose operands were produced on another stream than the one that flushes it: the branch is ordered
+    # behind every (tracked) side stream this pass has forked, not only the current one
+    _wait_side_streams(br.stream, dev)
+    with torch.cuda.stream(br.stream):
+        _flush_calls(calls)
+        _flush_gemms(gemms)
+        _flush(segs)
+    br.keep += [g["keep"] for g in gemms + calls + segs]
 
 
 def _dw_flush_pending(dev):
-    pend = _DW_PENDING.get(dev)
-    if not pend or not (pend[0] or pend[1] or pend[2]):
-        return
-    gemms, calls, segs = pend[0], pend[1], pend[2]
-    _DW_PENDING[dev] = [[], [], [], 0]
-    st = _DW_STREAM[dev]
-    st.wait_stream(torch.cuda.current_stream(dev))
-    # a batch may hold problems whose operands were produced on another stream than the one that flushes it: the branch is ordered
-    # behind every (tracked) side stream this pass has forked, not only the current one
-    for d2, s2 in list(_SIDE_USED):
-        if d2 == dev and s2 != st:
-            st.wait_stream(s2)
-    with torch.cuda.stream(st):
-        _flush_calls(calls)
-        _flush_gemms(gemms)
-        if DW_SUMS_LATE:
-            _DW_SUMS.setdefault(dev, []).extend(segs)      # ... summed at the join, 32 segments per launch
-        else:
-            _flush(segs)
-    _DW_KEEP.append((dev, [g["keep"] for g in gemms] + [c["keep"] for c in calls], [g["keep"] for g in segs]))
+    br = _DW[dev]
+    gemms, calls, segs = br.gemms, br.calls, br.segs
+    if gemms or calls or segs:
+        br.gemms, br.calls, br.segs, br.nbytes = [], [], [], 0
+        _dw_fork(dev, gemms, calls, segs)
 
 
 def _dw_join(final=True):
     """the stream that reads gradients waits for the weight-gradient branch.  Only the FINAL join (the end of the backward pass, on
     the stream backward() was called from) releases the tensors and forgets the branch: a join in the middle -- a backward function
     that has to read a sum, possibly running on a prompt module's own stream -- makes ITS stream wait and leaves the rest as it is."""
-    for dev in list(_DW_HELD):
-        _dw_release_held(dev)
-    for dev in list(_DW_PENDING):
+    for dev in _DW:
         _dw_flush_pending(dev)
-    for dev, segs in list(_DW_SUMS.items()):
-        if segs:
-            _DW_SUMS[dev] = []
-            with torch.cuda.stream(_DW_STREAM[dev]):      # behind the GEMMs that wrote the partials (same stream)
-                _flush(segs)
-    if _DW_KEEP:
-        for dev in {k[0] for k in _DW_KEEP}:
-            torch.cuda.current_stream(dev).wait_stream(_DW_STREAM[dev])
-        if final:
-            del _DW_KEEP[:]
+    for dev, br in _DW.items():
+        if br.keep:
+            torch.cuda.current_stream(dev).wait_stream(br.stream)
+            if final:
+                br.keep = []
     # ... and for every other tracked side stream this backward pass has forked (the prompt gate's): work that autograd issued on one
     # of them behind its last explicit join is ordered before the hand-over here, not by luck
-    for dev, st in list(_SIDE_USED):
-        torch.cuda.current_stream(dev).wait_stream(st)
+    for dev in {d for d, _ in _SIDE_USED}:
+        _wait_side_streams(torch.cuda.current_stream(dev), dev)
     if final:
         _SIDE_USED.clear()
 
@@ -444,8 +401,6 @@ def reduce_block(part, r0, nr, c0, nc, out, transpose=False, immediate=False):
         dst_ld, dcs = out.stride(0), 1
     _submit(dict(src=part.data_ptr() + 4 * (r0 * Cc + c0), dst=out.data_ptr(), n=nc, stride=part.stride(0), sbs=0, dbs=0, nsplit=nsplit,
                  nbatch=1, rows=max(nr, 1), dcs=dcs, src_ld=Cc, dst_ld=dst_ld, keep=(part, out)), immediate)
-    if nr == 1:      # the C side treats rows <= 1 as the 1-D form: identical addressing for a single row
-        pass
     return out
 
 
@@ -1435,7 +1390,7 @@ def spectral_dqkv_bwd_fits(C, heads, H, W, dtype):
     return SPECTRAL_BWD_FUSED and dtype in _HALF and bool(_lib.load().mphsir_spectral_dqkv_bwd_fits(C, heads, H, W, _DT[dtype]))
 
 
-def spectral_dqkv_bwd(qk, d_out, t, W2, MbT, w9, B, H, W, C, heads, nblk=None, round_dall=False, vscale=None):
+def spectral_dqkv_bwd(qk, d_out, t, W2, MbT, w9, B, H, W, C, heads, nblk=None, round_dall=False):
     """dt (M, 3C) and the tap gradients (3C, 9) of the channel attention from q|k (M, 2C), d_out (M, C), t (M, 3C), the per-sample
     matrices W2 (B, 2C, 2C) / MbT (B, C, C) and the taps w9 fp32 [9][3C]:  dv = d_out M_b, [dq|dk] = [q|k] W2^T, then both gradients of
     the depthwise conv -- [dq|dk|dv] stays on the chip (include/mphsir.h).  nblk: tile ranges (x channel slabs = workgroups)."""
@@ -1458,7 +1413,6 @@ def spectral_dqkv_bwd(qk, d_out, t, W2, MbT, w9, B, H, W, C, heads, nblk=None, r
     a.QK, a.ldqk, a.DO, a.lddo, a.T, a.ldt = _p(qk), qk.stride(0), _p(d_out), d_out.stride(0), _p(t), t.stride(0)
     a.W2, a.MbT, a.w9, a.ldw, a.dT, a.lddt, a.part = _p(W2), _p(MbT), _p(w9), w9.stride(0), _p(dt), 3 * C, _p(part)
     a.B, a.H, a.W, a.C, a.heads, a.nblk, a.round_dall = B, H, W, C, heads, nblk, int(round_dall)
-    a.vscale = _p(vscale)
     _lib.check(lib.mphsir_spectral_dqkv_bwd(ctypes.byref(a), _DT[qk.dtype], _stream(qk)), "spectral_dqkv_bwd")
     hd = C // heads
     _acct("spectral_dqkv_bwd", M * (2.0 * C * C + 8.0 * C * hd + 108.0 * C), 10.0 * M * C * qk.element_size() + part.numel() * 4)
@@ -1579,17 +1533,16 @@ def gated_mlp_wgrad(xn, dm, W1, b1, W2T, hid, nch=None, ranges=None):
     return dW1, db1[0], dW2, db2
 
 
-def combine_bwd(dy, sa, gate, keep, shift, want_dout=True):
-    """dy, sa (B,H,W,C) -> (d_out (= dy when keep is None; None with want_dout=False: the consumers apply keep themselves), d_sa,
-    dgate (B*nW,C) fp32)."""
+def combine_bwd(dy, sa, gate, keep, shift):
+    """dy, sa (B,H,W,C) -> (d_out (= dy when keep is None), d_sa, dgate (B*nW,C) fp32)."""
     lib = _lib.load()
     _check(dy, sa, gate, keep)
     B, H, W, C = dy.shape
     assert dy.is_contiguous() and sa.is_contiguous()
-    d_out = (torch.empty_like(dy) if want_dout else None) if keep is not None else dy
+    d_out = torch.empty_like(dy) if keep is not None else dy
     d_sa = torch.empty_like(dy)
     dgate = torch.empty_like(gate)
-    _lib.check(lib.mphsir_combine_bwd(_p(dy), _p(sa), _p(gate), _p(keep), _p(d_out) if (keep is not None and want_dout) else None, _p(d_sa),
+    _lib.check(lib.mphsir_combine_bwd(_p(dy), _p(sa), _p(gate), _p(keep), _p(d_out) if keep is not None else None, _p(d_sa),
                                       _p(dgate), B, H, W, C, shift, _DT[dy.dtype], _stream(dy)), "combine_bwd")
     _acct("combine_bwd", 4.0 * dy.numel(), 4.0 * dy.numel() * dy.element_size())
     return d_out, d_sa, dgate
@@ -1823,80 +1776,40 @@ def fold_bwd_forms_dm(N, C, heads, dtype):
     return dtype in _HALF and 0 < N <= FOLD_BWD_DM_MAX_TOKENS and N % 64 == 0 and (C // heads) in (32, 48, 64)      # (96-wide heads: the token tiles do not fit beside the 150 KB the kernel already takes)
 
 
-GDFN_DW_BWD = os.environ.get("MPHSIR_GDFN_DW_BWD", "0") == "1"      # gate backward + depthwise backward of the GDFN in one launch: correct, 1 GB per step less traffic, but level in A/B and +50 us in the serial trace (803 against 751 us for the four GDFNs): OFF
-GDFN_DW_BWD_WGS = int(os.environ.get("MPHSIR_GDFN_DW_BWD_WGS", "2048"))      # four rounds of resident workgroups (measured: 88 ranges x 22 slabs 333 us, 16 ranges 425)
-
-
-def gdfn_dw_bwd_fits(H, W, HP, dtype):
-    return GDFN_DW_BWD and dtype in _HALF and bool(_lib.load().mphsir_gdfn_dw_bwd_fits(H, W, HP, _DT[dtype]))
-
-
-def gdfn_dw_bwd(t, w9, du, B, H, W, nblk=None, round_mid=False):
-    """t (M, 2HP) = project_in(LN(x)), du (M, HP) contiguous, w9 fp32 [9][2HP] -> (u (M, HP), dt (M, 2HP), tap-gradient partials
-    (nblk, 9, 2HP)): the conv is recomputed on every tile's halo, [d x1 | d x2] stays on the chip (include/mphsir.h)."""
-    lib = _lib.load()
-    _check(t, w9, du)
-    M, HP = du.shape
-    assert t.shape == (M, 2 * HP) and t.is_contiguous() and du.is_contiguous() and M == B * H * W and w9.shape == (9, 2 * HP) and w9.stride(1) == 1
-    nslab = HP // 16
-    tiles = B * (H // 8) * (W // 16)
-    if nblk is None:
-        nblk = max(1, min(tiles, GDFN_DW_BWD_WGS // nslab))
-        if nblk >= 8:
-            nblk = nblk // 8 * 8
-    u = torch.empty((M, HP), dtype=t.dtype, device=t.device)
-    dt = torch.empty((M, 2 * HP), dtype=t.dtype, device=t.device)
-    part = torch.empty((nblk, 9, 2 * HP), dtype=torch.float32, device=t.device)
-    _lib.check(lib.mphsir_gdfn_dw_bwd(_p(t), _p(w9), w9.stride(0), _p(du), _p(u), _p(dt), _p(part), nblk, B, H, W, HP, int(round_mid),
-                                      _DT[t.dtype], _stream(t)), "gdfn_dw_bwd")
-    _acct("gdfn_gate_bwd", M * HP * (40.0 + 72.0), (2.0 * 1.9 + 1.4 + 1.0 + 2.0) * M * HP * t.element_size())
-    return u, dt, part
-
-
-def spectral_fold_bwd(gp, sp, temperature, Wo, dM, dtype, reduce=True, d_out=None, v=None, dm_scale=None, w2_blocks=False):
+def spectral_fold_bwd(gp, sp, temperature, Wo, dM, dtype, reduce=True, d_out=None, v=None, w2_blocks=False):
     """-> W2 (B,2C,2C) in `dtype`, dWo (C,C) fp32, dtemp (heads,) fp32 (reduce=False: the per-sample partials
     (B,C,C) / (B,heads) instead, for the caller to pass to reduce_parts).  dM=None with d_out, v (B*N, C) in `dtype`: dM is formed in
     the kernel (fold_bwd_forms_dm)."""
     lib = _lib.load()
     B, nsplit, heads, hd, _ = gp.shape
     C = heads * hd
+    a = _lib.FoldBwdArgs()
     if dM is None:
         _check(gp, sp, temperature, Wo, d_out, v)
         N = d_out.shape[0] // B
         assert d_out.shape == (B * N, C) and v.shape == (B * N, C) and d_out.dtype == dtype and v.dtype == dtype and d_out.stride(1) == 1 and v.stride(1) == 1
         assert fold_bwd_forms_dm(N, C, heads, dtype)
-        W2 = torch.empty((B, 2 * C, 2 * C), dtype=dtype, device=gp.device)
-        dWo = torch.empty((B, C, C), dtype=torch.float32, device=gp.device)
-        dtemp = torch.empty((B, heads), dtype=torch.float32, device=gp.device)
-        a = _lib.FoldBwdArgs()
-        a.Gpart, a.Spart, a.temperature, a.Wo = _p(gp), _p(sp), _p(temperature), _p(Wo)
-        a.W2, a.dWo, a.dtemp = _p(W2), _p(dWo), _p(dtemp)
-        a.B, a.C, a.heads, a.nsplit, a.dM_nsplit = B, C, heads, nsplit, 0
+        a.dM_nsplit = 0
         a.DO, a.lddo, a.V, a.ldv, a.N = _p(d_out), d_out.stride(0), _p(v), v.stride(0), N
-        a.dm_scale = _p(dm_scale)
-        a.w2_blocks = 1 if w2_blocks else 0
-        _lib.check(lib.mphsir_spectral_fold_bwd(ctypes.byref(a), _DT[dtype], _stream(gp)), "spectral_fold_bwd")
-        _acct("spectral_fold_bwd", 4.0 * B * C * C * hd + 2.0 * B * N * C * C, 3.0 * B * C * C * 4 + 2.0 * B * N * C * d_out.element_size())
-        _acct("spectral_fold_bwd:dm", 0.0, 0.0)
-        if not reduce:
-            return W2, dWo, dtemp
-        return W2, reduce_parts(dWo), reduce_parts(dtemp)
-    _check(gp, sp, temperature, Wo, dM)
-    # dM (B, C, C), or (B, splits, C, C): the raw split partials of the token-reduction GEMM (gemm_tn(..., reduce=False)) -- the kernel
-    # sums them in split order while it stages them, so no ordered-sum launch sits between the two
-    dm_nsplit = dM.shape[1] if dM.dim() == 4 else 1
-    assert dM.shape[0] == B and dM.shape[-2:] == (C, C) and dM.dtype == torch.float32 and dM.is_contiguous()
+    else:
+        _check(gp, sp, temperature, Wo, dM)
+        # dM (B, C, C), or (B, splits, C, C): the raw split partials of the token-reduction GEMM (gemm_tn(..., reduce=False)) -- the kernel
+        # sums them in split order while it stages them, so no ordered-sum launch sits between the two
+        assert dM.shape[0] == B and dM.shape[-2:] == (C, C) and dM.dtype == torch.float32 and dM.is_contiguous()
+        a.dM, a.dM_nsplit = _p(dM), dM.shape[1] if dM.dim() == 4 else 1
     W2 = torch.empty((B, 2 * C, 2 * C), dtype=dtype, device=gp.device)
     dWo = torch.empty((B, C, C), dtype=torch.float32, device=gp.device)
     dtemp = torch.empty((B, heads), dtype=torch.float32, device=gp.device)
-    a = _lib.FoldBwdArgs()
-    a.Gpart, a.Spart, a.temperature, a.Wo, a.dM = _p(gp), _p(sp), _p(temperature), _p(Wo), _p(dM)
+    a.Gpart, a.Spart, a.temperature, a.Wo = _p(gp), _p(sp), _p(temperature), _p(Wo)
     a.W2, a.dWo, a.dtemp = _p(W2), _p(dWo), _p(dtemp)
-    a.B, a.C, a.heads, a.nsplit, a.dM_nsplit = B, C, heads, nsplit, dm_nsplit
-    a.dm_scale = _p(dm_scale)
+    a.B, a.C, a.heads, a.nsplit = B, C, heads, nsplit
     a.w2_blocks = 1 if w2_blocks else 0
     _lib.check(lib.mphsir_spectral_fold_bwd(ctypes.byref(a), _DT[dtype], _stream(gp)), "spectral_fold_bwd")
-    _acct("spectral_fold_bwd", 4.0 * B * C * C * hd, 3.0 * B * C * C * 4)
+    if dM is None:
+        _acct("spectral_fold_bwd", 4.0 * B * C * C * hd + 2.0 * B * N * C * C, 3.0 * B * C * C * 4 + 2.0 * B * N * C * d_out.element_size())
+        _acct("spectral_fold_bwd:dm", 0.0, 0.0)
+    else:
+        _acct("spectral_fold_bwd", 4.0 * B * C * C * hd, 3.0 * B * C * C * 4)
     if not reduce:
         return W2, dWo, dtemp
     return W2, reduce_parts(dWo), reduce_parts(dtemp)

@@ -3,7 +3,6 @@
 #   tools/lab/step_sweeps.sh ab NAME A B [bench flags]   A/B of one environment knob, twice each, on the training step
 #   tools/lab/step_sweeps.sh sweep "K=V [K=V]" ...          each environment setting (plus the default, first and last) twice round-robin: ms per step
 #   tools/lab/step_sweeps.sh side                         what each captured side branch buys (step, 512x512 forward, batch-16 forward)
-#   tools/lab/step_sweeps.sh graphenv                     HIP runtime knobs for graph replay (branch queues, packet capture), with lab chains
 #   tools/lab/step_sweeps.sh procs                        two / four bench processes on one GPU against one
 #   tools/lab/step_sweeps.sh serial TAG                   kernel trace of the step with EVERY side branch off (one stream): per-kernel own cost
 #                                                         -> gpurun_out/TAG_serial_replay_only.csv, TAG_serial_gaps.log
@@ -22,14 +21,9 @@ side)
   for X in "" "--forward-only --patch 512 --batch 1" "--forward-only --batch 16"; do
     echo "### $X"
     for e in "X=1" "MPHSIR_SIDE_BRANCH=0" "MPHSIR_DW_SIDE=0" "MPHSIR_DW_SIDE=1" "MPHSIR_PROMPT_SIDE=0" "MPHSIR_SIDE_BRANCH=0 MPHSIR_DW_SIDE=0" \
-             "MPHSIR_SIDE_BRANCH=0 MPHSIR_DW_SIDE=0 MPHSIR_PROMPT_SIDE=0" "MPHSIR_SIDE_BRANCH=0 MPHSIR_DW_SIDE=0 MPHSIR_PROMPT_SIDE=0 DEBUG_HIP_FORCE_GRAPH_QUEUES=1" "X=1"; do
+             "MPHSIR_SIDE_BRANCH=0 MPHSIR_DW_SIDE=0 MPHSIR_PROMPT_SIDE=0" "X=1"; do
       echo "$e: $(line $e)"
     done
-  done ;;
-graphenv)
-  for e in "X=1" "DEBUG_HIP_FORCE_GRAPH_QUEUES=1" "DEBUG_HIP_FORCE_GRAPH_QUEUES=2" "DEBUG_HIP_FORCE_GRAPH_QUEUES=4" "DEBUG_HIP_FORCE_GRAPH_QUEUES=8" \
-           "DEBUG_CLR_GRAPH_PACKET_CAPTURE=0" "DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 DEBUG_HIP_FORCE_GRAPH_QUEUES=4" "DEBUG_HIP_GRAPH_BATCH_SIZE=1024" "GPU_MAX_HW_QUEUES=8"; do
-    echo "=== $e"; env $e python3 tools/lab/stream_overlap.py 2>&1 | grep numel | cut -c1-260; echo "step: $(line $e)"
   done ;;
 procs)
   echo "batch 32 alone: $(line X=1)"; X="--batch 16"; echo "batch 16 alone: $(line X=1)"
@@ -46,5 +40,5 @@ serial)
   python3 tools/diag/step_gaps.py gpurun_out/${tag}_serial_trace 12 flat_adamw gpurun_out/${tag}_serial_step_launches.csv > gpurun_out/${tag}_serial_gaps.log 2>&1
   find gpurun_out/${tag}_serial_trace -name "*.csv" -delete 2>/dev/null
   head -3 gpurun_out/${tag}_serial_gaps.log ;;
-*) echo "modes: ab side graphenv procs serial"; exit 2 ;;
+*) echo "modes: ab side procs serial"; exit 2 ;;
 esac
