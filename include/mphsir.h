@@ -725,6 +725,44 @@ typedef struct mphsir_degrade_args {
 } mphsir_degrade_args;
 int mphsir_degrade_batch(const mphsir_degrade_args* a, void* stream);
 
+/* ---- training patches cut out of a resident scene store: gather + per-patch min-max normalisation, one launch pair ------------------------
+ * The store (mp-hsir_amd/scene_store.py) keeps every level of every scene in ONE fp32 arena: level l is a contiguous [C][H_l][W_l] cube
+ * at element offset off_l.  A batch is B records (level, y, x): the C x P x P window p of the level with its top-left corner at (y, x).
+ *   out [B][C][P][P] fp32 = (p - min p) / (max p - min p)
+ * with min / max over the WHOLE window in fp32 and two subtractions and one correctly rounded division per element: equal, as floats, to
+ * what numpy gives on the fp32 level ((p - p.min()) / (p.max() - p.min()), the reference's utils/image_utils.py:437-439).  A NaN anywhere
+ * in the window makes the whole patch NaN (as np.min does), a constant window is all NaN (0 / 0), +-inf follow IEEE arithmetic.
+ *   levels       DEVICE int64 [n_levels][3]: {element offset, H, W} of level l -- 64-bit: a real store exceeds 2^31 elements
+ *   levels_host  HOST copy of the same table, read during the call and validated: 0 <= offset, offset + C H W <= arena_elems,
+ *                P <= H, P <= W, H * W < 2^31; the two copies must agree (the device copy is what the kernels read)
+ *   records      DEVICE int32 [n_records][3]: {level, y, x}
+ *   index        DEVICE int64 [B]: sample b is records[index[b]]; NULL: sample b is records[b] (n_records >= B: per-sample triples)
+ * The device level table is TRUSTED to equal levels_host (a differing H or W could make H - P negative and move reads out of the arena);
+ * what selects a window is not: index is clamped into [0, n_records), level into [0, n_levels), y into [0, H - P], x into [0, W - P],
+ * so with two equal level tables that passed the host check no launch reads outside the arena whatever index and records hold.
+ * Launch 1: one workgroup per (sample, band) plane writes {min, max} of the plane (both NaN when it holds one) to workspace [B][C][2];
+ * launch 2: one workgroup per plane combines its sample's C pairs, reads the plane again and writes normalised rows as 16-byte vectors.
+ * Rows are read as 16-byte vectors when every row start is 16-byte aligned (W % 4 == 0 and an aligned window origin), element-wise
+ * otherwise.  No atomics, no zero-fill, nothing read back by the host: bitwise reproducible and capturable; a captured pair replays with
+ * whatever index / records hold then.  workspace: mphsir_patch_sample_workspace_bytes(B, C) = 8 B C bytes, 8-byte aligned.
+ * MPHSIR_EINVAL: P not a positive multiple of 4 or > 4096, B or C outside 1..65535, out not 16-byte aligned, a level the window does not
+ * fit into or that leaves the arena, a workspace too small; nothing is launched then.                                                  */
+typedef struct mphsir_patch_sample_args {
+    uint32_t struct_size;
+    const float* arena;
+    const int64_t* levels;
+    const int64_t* levels_host;
+    const int32_t* records;
+    const int64_t* index;
+    float* out;
+    void* workspace;
+    int64_t workspace_bytes;
+    int64_t arena_elems;
+    int32_t n_levels, n_records, B, C, P;
+} mphsir_patch_sample_args;
+int64_t mphsir_patch_sample_workspace_bytes(int32_t B, int32_t C);
+int mphsir_patch_sample(const mphsir_patch_sample_args* a, void* stream);
+
 /* ---- fused AdamW over the flat parameter arena ---------------------------------------------------
  * One decoupled-weight-decay Adam step on n contiguous fp32 parameters (n % 4 == 0) with gradient g,
  * moments m, v; g is multiplied by grad_scale first (1/world_size after a sum all-reduce).
@@ -822,7 +860,9 @@ int mphsir_l1_clamp_loss(const float* y, const float* clean, float* grad, float*
 #define MPHSIR_K_SCENE 32
 #define MPHSIR_K_QUALITY 33
 #define MPHSIR_K_DEGRADE 34
-#define MPHSIR_K_COUNT 35
+#define MPHSIR_K_PATCH_SAMPLE 35      /* launch 1 of mphsir_patch_sample (min / max per plane) */
+#define MPHSIR_K_PATCH_NORMALISE 36   /* launch 2 (combine + normalise): ids of their own, so that the timer tells the two apart */
+#define MPHSIR_K_COUNT 37
 int mphsir_prof_enable(int kid);   /* kid < 0 disables */
 int mphsir_prof_read(int* launches, float* total_ms);
 const char* mphsir_kernel_name(int kid);

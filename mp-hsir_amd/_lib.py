@@ -169,6 +169,12 @@ class DegradeArgs(_Args):
                [(n, c_int32) for n in ("B", "C", "H", "W", "T", "K", "F")]
 
 
+class PatchSampleArgs(_Args):
+    """mirror of struct mphsir_patch_sample_args"""
+    _fields_ = _SZ + [(n, c_void_p) for n in ("arena", "levels", "levels_host", "records", "index", "out", "workspace")] + \
+               [("workspace_bytes", c_int64), ("arena_elems", c_int64)] + [(n, c_int32) for n in ("n_levels", "n_records", "B", "C", "P")]
+
+
 class TnProblem(ctypes.Structure):
     """mirror of struct mphsir_gemm_tn_problem"""
     _fields_ = [("A", c_void_p), ("lda", c_int64), ("B", c_void_p), ("ldb", c_int64), ("Cpart", c_void_p), ("colsum_part", c_void_p),
@@ -273,6 +279,8 @@ _SYMBOLS = {
     "mphsir_quality_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "mphsir_quality": (c_int, [ctypes.POINTER(QualityArgs), c_void_p]),
     "mphsir_degrade_batch": (c_int, [ctypes.POINTER(DegradeArgs), c_void_p]),
+    "mphsir_patch_sample_workspace_bytes": (c_int64, [c_int32, c_int32]),
+    "mphsir_patch_sample": (c_int, [ctypes.POINTER(PatchSampleArgs), c_void_p]),
     "mphsir_l1_clamp_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
 }
 

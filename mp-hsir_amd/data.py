@@ -159,3 +159,77 @@ class PatchDBSource:
             clean = degrade.interpolate_bands(clean, 31)
         degraded, clean, prompt = self.syn(clean)
         return [names, prompt[:, 0]], degraded, clean, prompt
+
+
+class SceneStoreSource:
+    """PatchDBSource's surface over a scene_store.SceneStore resident on the device: the same seeded permutation
+    (RandomState(seed).permutation(len * repeat)[rank::world], drop_last, modulo indexing), so over the same records it hands out the same
+    batches in the same order -- but a step is a slice of the epoch's permutation (uploaded once per epoch from pinned memory), one
+    ops.patch_sample launch pair and the synthesiser: no host bytes, and with fused_degrade no blocking host synchronisation.
+    jitter: every sample's origin is moved by a uniform offset in [0, stride of its level) per axis, clipped to the level; a moved window
+    that touches the mask falls back to the record's own origin (four look-ups in the mask level's integral image, merged with
+    torch.where).  The reference cannot do this; off by default.  `last_origins` gives the (B,3) int32 {level, y, x} of the last batch."""
+
+    def __init__(self, store, batch, de_types, data_type, device, seed=2024, rank=0, world=1, repeat=1, fused_degrade=False, jitter=False):
+        self.store, self.batch, self.device, self.data_type = store, batch, torch.device(device), data_type
+        self.rank, self.world, self.repeat, self.jitter = rank, world, repeat, bool(jitter)
+        self.rng = np.random.RandomState(seed)                       # same permutation on every rank, then sharded
+        self.syn = degrade.DegradationSynthesizer(data_type, de_types, device, seed + 7919 * rank + 1, fused=fused_degrade)
+        self.order, self.order_dev, self.pos, self._pin = None, None, 0, None
+        self.gen = torch.Generator(device=self.device).manual_seed(seed + 7919 * rank + 2) if self.jitter else None
+        self._last = None
+        if self.jitter:
+            self.sat, self.sat_off = store.mask_sat()
+
+    def steps_per_epoch(self):
+        return len(self.store) * self.repeat // (self.batch * self.world)
+
+    def _next_slice(self):
+        if self.order is None or self.pos + self.batch > len(self.order):
+            perm = self.rng.permutation(len(self.store) * self.repeat)
+            self.order, self.pos = perm[self.rank::self.world] % len(self.store), 0
+            host = torch.from_numpy(np.ascontiguousarray(self.order, dtype=np.int64))
+            if self.device.type == "cuda":
+                host = host.pin_memory()
+            self._pin = host                                          # stays alive while the copy may be in flight
+            self.order_dev = host.to(self.device, non_blocking=True)
+        lo = self.pos
+        self.pos += self.batch
+        return self.order[lo:lo + self.batch], self.order_dev[lo:lo + self.batch]
+
+    def _jittered(self, idx):
+        st, P = self.store, self.store.patch
+        rec = st.records.index_select(0, idx).to(torch.int64)
+        lvl, y, x = rec[:, 0], rec[:, 1], rec[:, 2]
+        lv = st.levels.index_select(0, lvl)
+        H, W = lv[:, 1], lv[:, 2]
+        stride = st.level_stride.index_select(0, lvl).to(torch.float32)
+        u = torch.rand((2, idx.shape[0]), generator=self.gen, device=self.device)
+        dy = torch.minimum((u[0] * stride).to(torch.int64), stride.to(torch.int64) - 1)
+        dx = torch.minimum((u[1] * stride).to(torch.int64), stride.to(torch.int64) - 1)
+        y2, x2 = torch.minimum(y + dy, H - P), torch.minimum(x + dx, W - P)
+        base, pitch = self.sat_off.index_select(0, lvl), W + 1
+        hit = (self.sat[base + (y2 + P) * pitch + x2 + P] - self.sat[base + y2 * pitch + x2 + P]
+               - self.sat[base + (y2 + P) * pitch + x2] + self.sat[base + y2 * pitch + x2])
+        ok = hit == 0
+        return torch.stack([lvl, torch.where(ok, y2, y), torch.where(ok, x2, x)], dim=1).to(torch.int32).contiguous()
+
+    @property
+    def last_origins(self):
+        """(B,3) int32 {level, y, x} of the last batch on the device (None before the first); without jitter it is gathered from the record
+        table here, on request, not in next()"""
+        if self._last is None or self.jitter:
+            return self._last
+        return self.store.records.index_select(0, self._last)
+
+    def next(self):
+        order, idx = self._next_slice()
+        names = [self.store.names[int(i)] for i in order]
+        if self.jitter:
+            self._last = self._jittered(idx)
+            clean = self.store.sample_at(self._last)
+        else:
+            self._last = idx                                          # a view of the epoch's permutation: nothing is launched for it
+            clean = self.store.sample(idx)
+        degraded, clean, prompt = self.syn(clean)
+        return [names, prompt[:, 0]], degraded, clean, prompt

@@ -839,6 +839,39 @@ def degrade_batch(clean, plan, *, seed, ordinal, draws=None, out=None):
     return out
 
 
+def patch_sample(arena, levels, levels_host, records, index, C, P, out=None, workspace=None):
+    """The batch of training patches a scene store hands out (scene_store.SceneStore, include/mphsir.h): arena (fp32, 1-D): every level of
+    every scene; levels (n_levels,3) int64 on the device {element offset, H, W} and levels_host, the same table on the host (validated
+    there); records (n,3) int32 on the device {level, y, x}; index (B,) int64 on the device: sample b is records[index[b]], or None:
+    sample b is records[b].  -> out (B,C,P,P) fp32 = (p - min p) / (max p - min p) over each C x P x P window.  One launch pair on the
+    current stream, nothing read back."""
+    lib = _lib.load()
+    _check(arena, levels, records, index, out, workspace)
+    assert arena.dim() == 1 and arena.dtype == torch.float32 and arena.is_contiguous(), "patch_sample: the arena is a flat fp32 tensor"
+    assert levels.dim() == 2 and levels.shape[1] == 3 and levels.dtype == torch.int64 and levels.is_contiguous(), "patch_sample: levels is (n,3) int64"
+    assert levels_host.dtype == torch.int64 and levels_host.shape == levels.shape and levels_host.is_contiguous() and not levels_host.is_cuda, \
+        "patch_sample: levels_host is the host copy of levels"
+    assert records.dim() == 2 and records.shape[1] == 3 and records.dtype == torch.int32 and records.is_contiguous(), "patch_sample: records is (n,3) int32"
+    assert index is None or (index.dim() == 1 and index.dtype == torch.int64 and index.is_contiguous()), "patch_sample: index is (B,) int64"
+    B = records.shape[0] if index is None else index.shape[0]
+    nbytes = lib.mphsir_patch_sample_workspace_bytes(B, C)
+    if nbytes < 0:
+        raise RuntimeError("mp-hsir_amd: patch_sample refuses (B %d, C %d): both in 1..65535" % (B, C))
+    dev = arena.device
+    if workspace is None:
+        workspace = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+    assert workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.device == dev
+    if out is None:
+        out = torch.empty((B, C, P, P), dtype=torch.float32, device=dev)
+    assert out.shape == (B, C, P, P) and out.dtype == torch.float32 and out.is_contiguous() and out.device == dev
+    a = _lib.PatchSampleArgs(arena=_p(arena), levels=_p(levels), levels_host=_p(levels_host), records=_p(records), index=_p(index), out=_p(out),
+                             workspace=_p(workspace), workspace_bytes=workspace.numel() * 4, arena_elems=arena.numel(),
+                             n_levels=levels.shape[0], n_records=records.shape[0], B=B, C=C, P=P)
+    _lib.check(lib.mphsir_patch_sample(ctypes.byref(a), _stream(arena)), "patch_sample")
+    _acct("patch_sample", 0.0, 12.0 * out.numel())
+    return out
+
+
 def round_up(n, m):
     return (n + m - 1) // m * m
 

@@ -6,7 +6,7 @@ options.py (options.py:6-37), so its command lines (README.md:36,38) work unchan
 Like the reference, the namespace is built at import time (`from options import options as opt`);
 unknown flags are tolerated so that importing this module under pytest/torchrun does not abort.
 Additions (not present in the reference, all optional): --model, --precision, --steps_per_epoch, --graph,
---synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
+--synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade, --scene_dir, --crop_jitter.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
 into ['0','1'] (options.py:36) and `--classifier type=bool` treats any non-empty string as True.
 """
 import argparse
@@ -51,6 +51,9 @@ _FLAGS = [
                       "epoch + 1 (a checkpoint written by this script); 0 (default) = the reference's warm start: weights only, epoch 0")),
     ("--fused_degrade", dict(type=int, default=0, help="1: degrade every training batch in one HIP launch from a plan built without host "
                              "synchronisation (degrade.DegradationSynthesizer(fused=True); no poissonN); 0 (default): the tensor programs")),
+    ("--scene_dir", dict(type=str, default="", help="with --synthetic 0: a directory of .mat / .npy cubes; the scene pyramid is built once, kept in "
+                         "HBM, and every batch is cut out of it on the device (scene_store.SceneStore); excludes --db_path")),
+    ("--crop_jitter", dict(type=int, default=0, help="1 (with --scene_dir): move every patch origin by a uniform offset below its level's stride")),
 ]
 
 

@@ -10,7 +10,9 @@ Same loss (clamp + L1, :58-61), optimizer (AdamW(lr) defaults, :69), schedule (l
 warm start from a Lightning checkpoint by key+shape filtering with the `net.` prefix (:109-116) and a
 checkpoint every 50 epochs (:104).  Data: --synthetic 1 (default; datasets are not available offline) feeds
 data.SyntheticPatchSource; --synthetic 0 --db_path <dir> reads the reference's patch records (data.PatchDB, the LMDB
-record format in a flat file).  Either way the per-task degradations of --*_single_de_type are synthesised on the GPU
+record format in a flat file); --synthetic 0 --scene_dir <dir> builds the scene pyramid of the directory's .mat / .npy cubes
+once, keeps it in HBM and cuts every batch out of it on the device (scene_store.SceneStore, data.SceneStoreSource; --crop_jitter 1 moves
+the origins).  Either way the per-task degradations of --*_single_de_type are synthesised on the GPU
 (degrade.DegradationSynthesizer).  Checkpoints carry, besides the `net.`-prefixed state_dict, AdamW's moments and step
 count and the CLIP text-embedding table the model was built with.  --ckpt_path is the reference's warm start (weights whose
 key and shape match, epoch 0); --resume 1 additionally restores the optimizer state and continues at the saved epoch + 1.
@@ -25,10 +27,11 @@ import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from mp_hsir_amd.data import REMOTE_SENSING_SOURCES, PatchDB, PatchDBSource, SyntheticPatchSource  # noqa: E402
+from mp_hsir_amd.data import REMOTE_SENSING_SOURCES, PatchDB, PatchDBSource, SceneStoreSource, SyntheticPatchSource  # noqa: E402
 from mp_hsir_amd.engine import DataParallelEngine, warmup_cosine_lr  # noqa: E402
 from mp_hsir_amd.net.MP_HSIR import MP_HSIR_Net  # noqa: E402
 from mp_hsir_amd.options import options as opt  # noqa: E402
+from mp_hsir_amd.scene_store import SceneStore, scene_files  # noqa: E402
 
 MODELS = {"natural_scene": dict(in_channel=31, out_channel=31, dim=64, task_classes=6),     # train.py:44
           "remote_sensing": dict(in_channel=100, out_channel=100, dim=96, task_classes=7)}  # train.py:45
@@ -121,11 +124,28 @@ def main():
                                    de_types=de_types, data_type=data_type, fused_degrade=bool(opt.fused_degrade))
         steps_per_epoch = opt.steps_per_epoch
     else:
-        if not opt.db_path:
-            raise SystemExit("--synthetic 0 needs --db_path <directory with data.bin + meta_info.txt> (data.write_patch_db)")
-        keep_all = data_type == "natural_scene" or opt.all_sources          # dataset_utils.py:56 filters remote-sensing sources
-        db = PatchDB(opt.db_path, dataset_names=None if keep_all else REMOTE_SENSING_SOURCES)
-        src = PatchDBSource(db, opt.batch_size, de_types, data_type, dev, opt.seed, rank, world, opt.repeat, fused_degrade=bool(opt.fused_degrade))
+        if opt.db_path and opt.scene_dir:
+            raise SystemExit("--db_path and --scene_dir both given: train from the patch database OR from the scene store")
+        if not opt.db_path and not opt.scene_dir:
+            raise SystemExit("--synthetic 0 needs --db_path <directory with data.bin + meta_info.txt> (data.write_patch_db) or --scene_dir "
+                             "<directory of .mat / .npy cubes>")
+        if opt.scene_dir:
+            P = opt.patch_size
+            files = scene_files(opt.scene_dir)
+            if data_type == "remote_sensing" and not opt.all_sources:            # the filter --db_path applies to its records (dataset_utils.py:56)
+                files = [f for f in files if os.path.basename(f).startswith(REMOTE_SENSING_SOURCES)]
+                if not files:
+                    raise SystemExit("--scene_dir %s holds no scene of %s (pass --all_sources 1 to train on every file)" % (opt.scene_dir, ", ".join(REMOTE_SENSING_SOURCES)))
+            store = SceneStore(files, data_type, dev, patch=P, strides=(P, P // 2, P // 2))
+            if rank == 0:
+                print("scene store: %d records from %d levels, %.1f MB resident, %d degenerate" %
+                      (len(store), store.levels_host.shape[0], store.nbytes / 1e6, store.degenerate), flush=True)
+            src = SceneStoreSource(store, opt.batch_size, de_types, data_type, dev, opt.seed, rank, world, opt.repeat,
+                                   fused_degrade=bool(opt.fused_degrade), jitter=bool(opt.crop_jitter))
+        else:
+            keep_all = data_type == "natural_scene" or opt.all_sources          # dataset_utils.py:56 filters remote-sensing sources
+            db = PatchDB(opt.db_path, dataset_names=None if keep_all else REMOTE_SENSING_SOURCES)
+            src = PatchDBSource(db, opt.batch_size, de_types, data_type, dev, opt.seed, rank, world, opt.repeat, fused_degrade=bool(opt.fused_degrade))
         steps_per_epoch = src.steps_per_epoch()
     for epoch in range(start_epoch, opt.epochs):
         lr = warmup_cosine_lr(epoch, opt.lr, opt.epochs)
