@@ -2,6 +2,8 @@
 (include/mphsir.h): the backward functions below only sequence launches -- block / prompt-module data gradients, and
 every parameter gradient as a token-reduction GEMM (gemm_tn), column sum or ordered partial reduction.  There is no
 PyTorch-composite or library-GEMM path: a shape the kernels do not cover raises."""
+from collections import namedtuple
+
 import torch
 import torch.nn.functional as F
 
@@ -20,18 +22,24 @@ class SkipGrad:
         return dz
 
 
+# what a block of a BaseBlock is told about the skip: the SkipGrad holder, and whether the block is the first / the last of its BaseBlock
+Skip = namedtuple("Skip", "holder first last")
+
+
 def _skip_put(skip, dz, needed):
     """the res-gradient a last block returns: handed to the holder when there is one"""
     if not needed:
         return None
-    if skip is not None and skip[2]:
-        skip[0].dz = dz
+    if skip is not None and skip.last:
+        # a put on a full holder: the first block's backward of an earlier pass never ran (pruned node, exception mid-backward)
+        assert skip.holder.dz is None, "SkipGrad: a second skip gradient arrived before the first block's backward took the last one"
+        skip.holder.dz = dz
         return None
     return dz
 
 
 def _skip_take(skip):
-    return skip[0].take() if (skip is not None and skip[1]) else None
+    return skip.holder.take() if (skip is not None and skip.first) else None
 
 
 class _GatedMlp(torch.autograd.Function):
@@ -83,86 +91,110 @@ def _gated_mlp_backward(blk, k2, y, dz):
     return (dx.reshape(B, H, W, Cc), dln[0], dln[1], dW1, db1, dW2, db2)
 
 
-def channel_attention_bwd(d_out, t_q, t_k, t_v, w9q, w9k, w9v, v, gp, sp, Mb, MbT, temperature, wo, heads, B, H, W, qk=None):
-    """Backward of the folded channel attention  out = M_b v,  M_b = Wo blockdiag(softmax(normalised Gram)).
-
-    d_out (M,C); t_q/t_k/t_v: (B,H,W,*) views of the 1x1-conv outputs that fed dwconv_gram (channels-last,
-    C channels each); w9*: fp32 tap-major dw weights [9][C] views; v, gp, sp, Mb, MbT as saved by the forward.
-    Returns d(t_q), d(t_k), d(t_v) (B,H,W,C each), d(dw taps) (C,9) x3, d temperature (heads,), d Wo (C,C).
-    All HIP: dM = d_out^T v (gemm_tn), fold backward (one launch), then [dq|dk], dv and the depthwise backward (data + taps) in ONE
-    launch (ops.spectral_dqkv_bwd, 16-bit types, self-attention: q|k|v adjacent slices of one t) -- else per-sample token GEMMs +
-    the depthwise backward kernels."""
+def _fold_bwd(d_out, v, gp, sp, temperature, wo, heads, B, N, w2_blocks):
+    """front half of the channel attention backward (out = M_b v, M_b = Wo blockdiag(softmax(normalised Gram))): dM = d_out^T v and
+    the fold backward.  -> W2 (B,2C,2C) with [dq | dk] = [q | k] W2^T, and the partials of d Wo / d temperature."""
     C = v.shape[1]
-    N = H * W
-    M = B * N
     dt = v.dtype
     temp32, wo32 = temperature.detach().reshape(heads).float().contiguous(), wo.detach().reshape(C, C).float().contiguous()
-    joint = (t_q.data_ptr() + C * t_q.element_size() == t_k.data_ptr() and t_k.data_ptr() + C * t_k.element_size() == t_v.data_ptr()
-             and t_q.stride() == t_k.stride() == t_v.stride() and w9q.data_ptr() + 4 * C == w9k.data_ptr()
-             and w9k.data_ptr() + 4 * C == w9v.data_ptr())
-    fused = joint and t_q.stride(2) == 3 * C and w9q.stride(0) == 3 * C and ops.spectral_dqkv_bwd_fits(C, heads, H, W, dt)
-    # (the fused launch reads only each head's own column blocks of W2: the fold backward then writes nothing else -- 2 hd of 2C columns)
+    # (w2_blocks: the fused launch reads only each head's own column blocks of W2: the fold backward then writes nothing else -- 2 hd of 2C columns)
     if ops.fold_bwd_forms_dm(N, C, heads, dt):
         # small images (the lower pyramid levels): dM = d_out^T v is formed INSIDE the fold backward -- one launch fewer on the chain
-        W2, dwo_p, dtemp_p = ops.spectral_fold_bwd(gp, sp, temp32, wo32, None, dt, reduce=False, d_out=d_out.reshape(M, C), v=v.reshape(M, C), w2_blocks=fused)
-    else:
-        dM = ops.gemm_tn(d_out.reshape(B, N, C), v.reshape(B, N, C), reduce=False)    # (B, splits, C, C) fp32 partials: summed by the fold backward as it stages them
-        W2, dwo_p, dtemp_p = ops.spectral_fold_bwd(gp, sp, temp32, wo32, dM, dt, reduce=False, w2_blocks=fused)
-    # q, k of the forward: either kept by it (qk) or recomputed by the depthwise kernel; when q|k|v are adjacent channel
-    # slices of one tensor (self-attention) every depthwise pass runs once over the joint channel range.
-    if qk is not None:
-        pass                                                    # kept by the forward (dwconv_gram keep_qk)
-    elif joint:
-        qk = ops.dwconv3x3(torch.as_strided(t_q, (B, H, W, 2 * C), t_q.stride()), torch.as_strided(w9q, (9, 2 * C), w9q.stride()))
-    else:                                                       # cross attention: q and k come from different tensors -- both
-        qk = torch.empty((B, H, W, 2 * C), dtype=dt, device=v.device)      # depthwise outputs go straight into the halves of [q | k]
-        ops.dwconv3x3(t_q, w9q, out=qk[..., :C])
-        ops.dwconv3x3(t_k, w9k, out=qk[..., C:])
+        return ops.spectral_fold_bwd(gp, sp, temp32, wo32, None, dt, reduce=False, d_out=d_out.reshape(B * N, C), v=v.reshape(B * N, C), w2_blocks=w2_blocks)
+    dM = ops.gemm_tn(d_out.reshape(B, N, C), v.reshape(B, N, C), reduce=False)    # (B, splits, C, C) fp32 partials: summed by the fold backward as it stages them
+    return ops.spectral_fold_bwd(gp, sp, temp32, wo32, dM, dt, reduce=False, w2_blocks=w2_blocks)
+
+
+def _dqkv_tok(d_out, qk, W2, MbT, dwo_p, dtemp_p):
+    """[dq | dk | dv] (M,3C) as two per-sample token GEMMs into one buffer, the d Wo / d temperature sums between them.
+    -> (dall, dtemp, dwo)"""
+    M, C = d_out.shape
+    dall = torch.empty((M, 3 * C), dtype=d_out.dtype, device=d_out.device)
+    ops.gemm_tok(d_out, MbT, out=dall[:, 2 * C:])                                     # dv = d_out M_b
+    dwo, dtemp = ops.reduce_parts(dwo_p), ops.reduce_parts(dtemp_p)
+    ops.gemm_tok(qk.reshape(M, 2 * C), W2, out=dall[:, :2 * C])                       # [dq | dk]
+    return dall, dtemp, dwo
+
+
+def channel_attention_bwd_self(d_out, t, w9, v, gp, sp, MbT, temperature, wo, heads, qk=None):
+    """Backward of the folded self channel attention: q | k | v = dwconv3x3(t, w9), adjacent channel ranges of ONE tensor.
+
+    d_out (M,C); t (B,H,W,3C) contiguous: the 1x1-conv output that fed pass A; w9 (9,3C) fp32 contiguous: the tap-major dw weights;
+    v, gp, sp, MbT as saved by the forward; qk: q | k (M,2C) where the forward kept it, else it is recomputed here.
+    Returns dt (M,3C), dw (3C,9) fp32 (the parameter's layout), d temperature (heads,), d Wo (C,C).
+    All HIP: the front half (_fold_bwd), then [dq|dk], dv and the depthwise backward (data + taps) in ONE launch (ops.spectral_dqkv_bwd,
+    16-bit types) -- else per-sample token GEMMs + the depthwise backward kernel over the joint channel range."""
+    C = v.shape[1]
+    assert t.dim() == 4 and t.shape[3] == 3 * C and t.is_contiguous(), \
+        "t must be one contiguous (B,H,W,3C) tensor, C = %d: shape %s, stride %s" % (C, tuple(t.shape), t.stride())
+    assert w9.dtype == torch.float32 and w9.shape == (9, 3 * C) and w9.is_contiguous(), \
+        "w9 must be one contiguous fp32 (9,3C) tensor, C = %d: %s, shape %s, stride %s" % (C, w9.dtype, tuple(w9.shape), w9.stride())
+    B, H, W, _ = t.shape
+    M = B * H * W
+    fused = ops.spectral_dqkv_bwd_fits(C, heads, H, W, v.dtype)
+    W2, dwo_p, dtemp_p = _fold_bwd(d_out, v, gp, sp, temperature, wo, heads, B, H * W, fused)
+    if qk is None:                                              # not kept by the forward (dwconv_gram keep_qk): one pass over q | k
+        qk = ops.dwconv3x3(t[..., :2 * C], w9[:, :2 * C])
     if fused:
         # ONE launch from the fold backward's matrix to dt: dv = d_out M_b and [dq | dk] = [q | k] W2^T are formed per halo tile on the
         # matrix cores and fed to the depthwise backward in LDS -- [dq | dk | dv] (3C per token) is neither written nor read back
         dwo, dtemp = ops.reduce_parts(dwo_p), ops.reduce_parts(dtemp_p)
-        t_all = torch.as_strided(t_q, (M, 3 * C), (3 * C, 1))
-        w9_all = torch.as_strided(w9q, (9, 3 * C), w9q.stride())
-        dt_all, dw_all = ops.spectral_dqkv_bwd(qk.reshape(M, 2 * C), d_out, t_all, W2, MbT, w9_all, B, H, W, C, heads)
-        dt_all = dt_all.reshape(B, H, W, 3 * C)
-        return (dt_all[..., :C], dt_all[..., C:2 * C], dt_all[..., 2 * C:], dw_all[:C], dw_all[C:2 * C], dw_all[2 * C:], dtemp, dwo)
-    dall = torch.empty((M, 3 * C), dtype=dt, device=v.device)
-    ops.gemm_tok(d_out, MbT, out=dall[:, 2 * C:])                                     # dv = d_out M_b
-    dwo, dtemp = ops.reduce_parts(dwo_p), ops.reduce_parts(dtemp_p)
-    ops.gemm_tok(qk.reshape(M, 2 * C), W2, out=dall[:, :2 * C])                       # [dq | dk]
+        dt_all, dw = ops.spectral_dqkv_bwd(qk.reshape(M, 2 * C), d_out, t.reshape(M, 3 * C), W2, MbT, w9, B, H, W, C, heads)
+        return dt_all, dw, dtemp, dwo
+    dall, dtemp, dwo = _dqkv_tok(d_out, qk, W2, MbT, dwo_p, dtemp_p)
+    # both gradients of the depthwise conv in one launch (dall read once)
+    dt_all, dw = ops.dwconv3x3_bwd(t, dall.reshape(B, H, W, 3 * C), w9, col_ranges=[(0, 3 * C)])
+    return dt_all.reshape(M, 3 * C), dw, dtemp, dwo
+
+
+def channel_attention_bwd_cross(d_out, tq, tkv, w9, v, gp, sp, MbT, temperature, wo, heads):
+    """Backward of the folded cross channel attention: q = dwconv3x3(tq), k | v = dwconv3x3(tkv).
+
+    d_out (M,C); tq (B,H,W,C), tkv (B,H,W,2C): the 1x1-conv outputs; w9 (9,3C) fp32: the taps of q | k | v.
+    Returns d tq (B,H,W,C), d tkv (M,2C), dw (3C,9) fp32, d temperature (heads,), d Wo (C,C).  d tkv and dw are each ONE buffer the
+    per-tensor launches write their parts of: no concatenation reads tap sums that may not have been launched yet
+    (ops.deferred_reductions)."""
+    B, H, W, C = tq.shape
+    M = B * H * W
+    dt = v.dtype
+    assert tkv.shape == (B, H, W, 2 * C) and w9.dtype == torch.float32 and w9.shape == (9, 3 * C), (tuple(tq.shape), tuple(tkv.shape), tuple(w9.shape))
+    tk, tv = tkv[..., :C], tkv[..., C:]
+    w9q, w9k, w9v = w9[:, :C], w9[:, C:2 * C], w9[:, 2 * C:]
+    W2, dwo_p, dtemp_p = _fold_bwd(d_out, v, gp, sp, temperature, wo, heads, B, H * W, False)
+    qk = torch.empty((B, H, W, 2 * C), dtype=dt, device=v.device)      # q and k of the forward, recomputed: both depthwise outputs go
+    ops.dwconv3x3(tq, w9q, out=qk[..., :C])                            # straight into the halves of [q | k]
+    ops.dwconv3x3(tk, w9k, out=qk[..., C:])
+    dall, dtemp, dwo = _dqkv_tok(d_out, qk, W2, MbT, dwo_p, dtemp_p)
     dall4 = dall.reshape(B, H, W, 3 * C)
-    if joint:
-        t_all = torch.as_strided(t_q, (B, H, W, 3 * C), t_q.stride())
-        w9_all = torch.as_strided(w9q, (9, 3 * C), w9q.stride())
-        # both gradients of the depthwise conv in one launch (dall read once); dw_all (3C, 9): the parameter's layout
-        dt_all, dw_all = ops.dwconv3x3_bwd(t_all, dall4, w9_all, col_ranges=[(0, 3 * C)])
-        return (dt_all[..., :C], dt_all[..., C:2 * C], dt_all[..., 2 * C:], dw_all[:C], dw_all[C:2 * C], dw_all[2 * C:],
-                dtemp, dwo)
     dq4, dk4, dv4 = dall4[..., :C], dall4[..., C:2 * C], dall4[..., 2 * C:]
-    # the three tap gradients are row ranges of ONE buffer: the callers join them as a view (a cat would READ sums that may
-    # not have been launched yet, ops.deferred_reductions)
-    dw3 = torch.empty((3 * C, 9), dtype=torch.float32, device=v.device)
-    # d(t_k), d(t_v) as the halves of ONE buffer: the cross attention's caller takes them as [d t_k | d t_v] without a cat
     dkv = torch.empty((B, H, W, 2 * C), dtype=dt, device=v.device)
-    return (ops.dwconv3x3(dq4, w9q, flip=True), ops.dwconv3x3(dk4, w9k, flip=True, out=dkv[..., :C]), ops.dwconv3x3(dv4, w9v, flip=True, out=dkv[..., C:]),
-            ops.dwconv3x3_wgrad(t_q, dq4, col_ranges=[(0, C)], out=dw3[:C]), ops.dwconv3x3_wgrad(t_k, dk4, col_ranges=[(0, C)], out=dw3[C:2 * C]),
-            ops.dwconv3x3_wgrad(t_v, dv4, col_ranges=[(0, C)], out=dw3[2 * C:]), dtemp, dwo)
+    dw = torch.empty((3 * C, 9), dtype=torch.float32, device=v.device)
+    dtq = ops.dwconv3x3(dq4, w9q, flip=True)
+    ops.dwconv3x3(dk4, w9k, flip=True, out=dkv[..., :C])
+    ops.dwconv3x3(dv4, w9v, flip=True, out=dkv[..., C:])
+    ops.dwconv3x3_wgrad(tq, dq4, col_ranges=[(0, C)], out=dw[:C])
+    ops.dwconv3x3_wgrad(tk, dk4, col_ranges=[(0, C)], out=dw[C:2 * C])
+    ops.dwconv3x3_wgrad(tv, dv4, col_ranges=[(0, C)], out=dw[2 * C:])
+    return dtq, dkv.reshape(M, 2 * C), dw, dtemp, dwo
 
 
 _PG_KEYS = ("linear_down.weight", "linear_up.weight", "linear_prompt.weight", "prompt_param", "q.weight", "kv.weight",
             "proj.weight", "proj.bias")
 
 
-def _pass_a_infer(x2, wqkv, w9, B, H, W, C, heads, ln=None):
-    """pass A of the channel attention without a backward: (v, Gram partials, sum-of-squares partials).  One fused launch
-    (csrc/spectral_fused.hip) where the shape is covered, else the two-kernel path without its training outputs."""
-    if ops.qkv_dwconv_gram_fits(C, heads, H, W, x2.dtype):
-        v, gp, sp, _ = ops.qkv_dwconv_gram(x2, wqkv, w9, B, H, W, C, heads, ln=ln)
+def _pass_a(x2, wqkv, w9, B, H, W, C, heads, ln=None, keep=False):
+    """pass A of the channel attention from x2 (M,C): -> (v, Gram partials, sum-of-squares partials, t, qk).  One fused launch
+    (csrc/spectral_fused.hip) where the shape is covered, else the 1x1 GEMM + the depthwise / Gram kernel.  keep (training): t = qkv(LN(x2))
+    (M,3C) and q | k after the depthwise conv (M,2C: cheaper to keep than to recompute; None where the two-kernel path cannot emit it)
+    are returned for the backward, else both are None."""
+    if (ops.FUSED_TRAIN or not keep) and ops.qkv_dwconv_gram_fits(C, heads, H, W, x2.dtype):
+        v, gp, sp, _, *kept = ops.qkv_dwconv_gram(x2, wqkv, w9, B, H, W, C, heads, ln=ln, keep=keep)       # keep: ..., t, qk
     else:
         t = ops.gemm_tok(x2, wqkv, ln=ln)
-        v, gp, sp, _ = ops.dwconv_gram(t[:, :C], t[:, C:2 * C], t[:, 2 * C:], w9[:, :C], w9[:, C:2 * C], w9[:, 2 * C:], 3 * C, B, H, W, C, heads)
-    return v, gp, sp
+        v, gp, sp, _, *qk = ops.dwconv_gram(t[:, :C], t[:, C:2 * C], t[:, 2 * C:], w9[:, :C], w9[:, C:2 * C], w9[:, 2 * C:], 3 * C, B, H, W, C, heads,
+                                            keep_qk=keep)                                                # keep: ..., qk
+        kept = [t, *qk]
+    return (v, gp, sp, *kept) if keep else (v, gp, sp, None, None)
 
 
 def _pgsstb_attn_infer(blk, k1, x, fuse=False):
@@ -177,7 +209,7 @@ def _pgsstb_attn_infer(blk, k1, x, fuse=False):
     sa, mu, _ = ops.win_attn_fwd(x, pk["ln1"][0], pk["ln1"][1], pk["wqkv"], pk["bqkv"], pk["rpb"], pk["wproj"], pk["bproj"],
                                  pk["pg"], heads, shift, gate=False)
     sa2 = sa.reshape(-1, Cc)
-    v, gp, spart = _pass_a_infer(sa2, sp["wqkv"], sp["w9"], B, H, W, Cc, heads)
+    v, gp, spart, _, _ = _pass_a(sa2, sp["wqkv"], sp["w9"], B, H, W, Cc, heads)
     # the prompt gate forks AFTER pass A is issued (beside the fused pass A, whose workgroups fill the LDS of every CU, it costs
     # 2 % of the 512x512 forward): it runs beside the partial-sum reduction and the fold, three small latency-bound launches
     # (7.62 -> 7.58 ms)
@@ -195,35 +227,31 @@ def _self_channel_attn_infer(attn, ln, geom, t2):
     """a = t + M_b v (ref Attention :289-322 inside :476) under no_grad: fused pass A with the LayerNorm prologue."""
     B, H, W = geom
     pa = attn.packed(t2.dtype)
-    v, gp, sp = _pass_a_infer(t2, pa["wqkv"], pa["w9"], B, H, W, t2.shape[1], attn.num_heads, ln=ln.pair())
+    v, gp, sp, _, _ = _pass_a(t2, pa["wqkv"], pa["w9"], B, H, W, t2.shape[1], attn.num_heads, ln=ln.pair())
     return ops.gemm_tok(v, ops.spectral_fold(gp, sp, pa["temp"], pa["wo"], t2.dtype), epi=1, res=t2)
 
 
+# what the forward of a PGSSTB block's first residual branch keeps for its backward (qk: None where pass A could not emit it)
+_AttnSaved = namedtuple("_AttnSaved", "x sa gate mu oattn t v gp spart Mb MbT qk")
+
+
 def _pgsstb_attn_forward(blk, k1, x, fuse=False):
-    """forward of the first residual branch; returns (y, tensors kept for the backward).  fuse: y is left to the gated-MLP launch
-    (ops.gated_mlp_fwd branch=...: the operands are saved[6] = v, saved[9] = Mb, saved[1] = sa, saved[2] = gate) and None is returned."""
+    """forward of the first residual branch; returns (y, _AttnSaved).  fuse: y is left to the gated-MLP launch (ops.gated_mlp_fwd
+    branch=...: its operands are the saved v, Mb, sa, gate) and None is returned."""
     B, H, W, Cc = x.shape
     dt = x.dtype
     pk = blk.packed(dt)
     sp = blk.gobal_spectral_attn.packed(dt)
     heads, shift = blk.num_heads, blk.shift_size
-    w9 = sp["w9"]
     sa, mu, oattn = ops.win_attn_fwd(x, pk["ln1"][0], pk["ln1"][1], pk["wqkv"], pk["bqkv"], pk["rpb"], pk["wproj"],
                                      pk["bproj"], pk["pg"], heads, shift, save=True, gate=False)
     with ops.side_stream(sa, ops.SIDE_BRANCH) as br:      # the prompt gate (few workgroups, latency-bound) runs beside pass A
         gate = ops.pg_gate_fwd(mu, pk["pg"])
     sa2 = sa.reshape(-1, Cc)
-    # pass A; t and q | k after the depthwise conv are kept for the backward (q|k: 2C values per token, cheaper than
-    # recomputing them).  One fused launch where the kernel covers the shape, else 1x1 GEMM + depthwise/Gram kernel.
-    if ops.FUSED_TRAIN and ops.qkv_dwconv_gram_fits(Cc, heads, H, W, dt):
-        v, gp, spart, _, t, qk = ops.qkv_dwconv_gram(sa2, sp["wqkv"], w9, B, H, W, Cc, heads, keep=True)
-    else:
-        t = ops.gemm_tok(sa2, sp["wqkv"])
-        v, gp, spart, _, qk = ops.dwconv_gram(t[:, :Cc], t[:, Cc:2 * Cc], t[:, 2 * Cc:], w9[:, :Cc], w9[:, Cc:2 * Cc], w9[:, 2 * Cc:],
-                                              3 * Cc, B, H, W, Cc, heads, keep_qk=True)
+    v, gp, spart, t, qk = _pass_a(sa2, sp["wqkv"], sp["w9"], B, H, W, Cc, heads, keep=True)
     Mb, MbT, gp, spart = ops.spectral_fold(gp, spart, sp["temp"], sp["wo"], dt, transposed=True)   # keep the sums, drop the partials
     br.join()
-    saved = (x, sa, gate, mu, oattn, t, v, gp, spart, Mb, MbT) + ((qk,) if qk is not None else ())
+    saved = _AttnSaved(x, sa, gate, mu, oattn, t, v, gp, spart, Mb, MbT, qk)
     if fuse:
         return None, saved
     y = ops.gemm_tok(v, Mb, epi=2, res=x.reshape(-1, Cc), sa=sa2, gate=gate, keep=k1, geom=(H, W, shift))
@@ -231,11 +259,10 @@ def _pgsstb_attn_forward(blk, k1, x, fuse=False):
 
 
 def _pgsstb_attn_backward(blk, k1, saved, dy, extra=None):
-    """extra: a gradient of x from outside the block (SkipGrad), added to dx by the last launch.
+    """saved: the forward's _AttnSaved; extra: a gradient of x from outside the block (SkipGrad), added to dx by the last launch.
     backward of the first residual branch: (dx, d norm1.weight, d norm1.bias, d qkv.weight, d qkv.bias, d proj.weight, d proj.bias,
     d rpb table, d temperature, d spectral qkv, d spectral dw, d project_out, *d prompt-gate parameters (_PG_KEYS))"""
-    x, sa, gate, mu, oattn, t, v, gp, spart, Mb, MbT = saved[:11]
-    qk = saved[11] if len(saved) > 11 else None
+    x, sa, gate, mu, oattn = saved.x, saved.sa, saved.gate, saved.mu, saved.oattn
     B, H, W, Cc = x.shape
     dt = x.dtype
     M = B * H * W
@@ -256,16 +283,9 @@ def _pgsstb_attn_backward(blk, k1, saved, dy, extra=None):
             # check (the reference's own bf16 autocast: 2 %); the fp32 product of <= 512 rows costs nothing
             dmu, gpg = ops.pg_gate_bwd(mu, dgate, pk["pg"], factor_dtype=torch.float32 if f32_factors else dt)
         # (2) global spectral attention
-        t4 = t.reshape(B, H, W, 3 * Cc)
-        w9 = sp["w9"]
-        tq, tk, tv = t4[..., :Cc], t4[..., Cc:2 * Cc], t4[..., 2 * Cc:]
-        dtq, dtk, dtv, dwq, dwk, dwv, dtemp, dwo = channel_attention_bwd(
-            d_out.reshape(M, Cc), tq, tk, tv, w9[:, :Cc], w9[:, Cc:2 * Cc], w9[:, 2 * Cc:], v, gp, spart, Mb, MbT,
-            blk.gobal_spectral_attn.temperature, blk.gobal_spectral_attn.project_out.weight, heads, B, H, W, qk=qk)
-        if dtq.data_ptr() + Cc * dtq.element_size() == dtk.data_ptr() and dtq.stride(2) == 3 * Cc:
-            dt3 = torch.as_strided(dtq, (M, 3 * Cc), (3 * Cc, 1))
-        else:
-            dt3 = torch.cat([dtq, dtk, dtv], dim=-1).reshape(M, 3 * Cc)
+        dt3, d_sdw, dtemp, dwo = channel_attention_bwd_self(
+            d_out.reshape(M, Cc), saved.t.reshape(B, H, W, 3 * Cc), sp["w9"], saved.v, saved.gp, saved.spart, saved.MbT,
+            blk.gobal_spectral_attn.temperature, blk.gobal_spectral_attn.project_out.weight, heads, qk=saved.qk)
         d_sa = ops.gemm_tok(dt3, sp["wqkvT"], epi=1, res=d_sa.reshape(M, Cc))    # + dt Wqkv  (1x1 conv backward)
         d_sqkv = ops.gemm_tn(dt3, sa.reshape(M, Cc)).reshape(3 * Cc, Cc, 1, 1)
         dpg = tuple(gpg[k].reshape(getattr_path(blk.local_spectral_attn, k).shape) for k in _PG_KEYS)
@@ -287,11 +307,8 @@ def _pgsstb_attn_backward(blk, k1, saved, dy, extra=None):
                 dx = dx + extra
         dln = ops.reduce_parts(part)
         drpb = ops.reduce_parts(drpb)
-    d_sdw = _join_taps(dwq, dwk, dwv).reshape(3 * Cc, 1, 3, 3)
     return (dx, dln[0], dln[1], d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, drpb,
-            dtemp.reshape(heads, 1, 1), d_sqkv, d_sdw, dwo.reshape(Cc, Cc, 1, 1)) + tuple(dpg)
-
-
+            dtemp.reshape(heads, 1, 1), d_sqkv, d_sdw.reshape(3 * Cc, 1, 3, 3), dwo.reshape(Cc, Cc, 1, 1)) + tuple(dpg)
 
 
 class _PgsstbAttn(torch.autograd.Function):
@@ -306,7 +323,7 @@ class _PgsstbAttn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        return (None, None, None) + _pgsstb_attn_backward(ctx.blk, ctx.k1, ctx.saved_tensors, dy, extra=_skip_take(ctx.skip))
+        return (None, None, None) + _pgsstb_attn_backward(ctx.blk, ctx.k1, _AttnSaved(*ctx.saved_tensors), dy, extra=_skip_take(ctx.skip))
 
 
 _N_ATTN_PARAMS = 11 + len(_PG_KEYS)
@@ -324,7 +341,7 @@ class _Pgsstb(torch.autograd.Function):
         pk = blk.packed(x.dtype)
         z, y = ops.gated_mlp_fwd(x.reshape(-1, Cc), pk["ln2"][0], pk["ln2"][1], pk["W1"], pk["b1"], pk["W2"], pk["b2"], keep=k2, rows_per_batch=H * W,
                                  res=None if res is None else res.reshape(-1, Cc),
-                                 branch=dict(v=saved[6], Mb=saved[9], sa=saved[1].reshape(-1, Cc), gate=saved[2], keep=k1,
+                                 branch=dict(v=saved.v, Mb=saved.Mb, sa=saved.sa.reshape(-1, Cc), gate=saved.gate, keep=k1,
                                              geom=(H, W, blk.shift_size), want_y=True))
         ctx.blk, ctx.k1, ctx.k2, ctx.skip = blk, k1, k2, skip
         ctx.save_for_backward(y.reshape(B, H, W, Cc), *saved)
@@ -332,25 +349,11 @@ class _Pgsstb(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz):
-        y, saved = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        y, *saved = ctx.saved_tensors
         d_res = _skip_put(ctx.skip, dz, ctx.needs_input_grad[3])       # (before the take: a one-block BaseBlock is first and last)
         gm = _gated_mlp_backward(ctx.blk, ctx.k2, y, dz)
-        ga = _pgsstb_attn_backward(ctx.blk, ctx.k1, saved, gm[0], extra=_skip_take(ctx.skip))
+        ga = _pgsstb_attn_backward(ctx.blk, ctx.k1, _AttnSaved(*saved), gm[0], extra=_skip_take(ctx.skip))
         return (None, None, None, d_res, None) + ga + gm[1:]
-
-
-def _join_taps(*dw):
-    """(C,9) tap gradients of adjacent channel ranges -> (sum C, 9); a view when they already are row slices of one buffer."""
-    w0 = dw[0]
-    ok, off = True, w0.data_ptr()
-    for w in dw:
-        ok = (ok and w.data_ptr() == off and w.is_contiguous()
-              and w.untyped_storage().data_ptr() == w0.untyped_storage().data_ptr())
-        off += w.numel() * w.element_size()
-    if ok:
-        return torch.as_strided(w0, (sum(w.shape[0] for w in dw), 9), (9, 1))
-    ops.flush_deferred()            # the cat reads the sums: they must have been launched
-    return torch.cat(dw, dim=0)
 
 
 def getattr_path(mod, dotted):
@@ -384,6 +387,11 @@ def pgsstb(blk, x, k1, k2, res=None, skip=None):
 
 
 # ---- GDFN / channel attention sub-chains ------------------------------------------------------------
+def _gdfn_fuses(B, H, W, D, HP, dtype):
+    """the whole GDFN block as one launch: the fused kernel covers the shape and the image fills the chip with its pixel tiles"""
+    return B * H * W >= ops.GDFN_FUSED_MIN_PIXELS and ops.gdfn_fused_fits(D, HP, H, W, dtype)
+
+
 class _GdfnRes(torch.autograd.Function):
     """y = a + project_out(gelu(x1) * x2), [x1|x2] = dwconv(project_in(LN(a)))   (ref FFN :251-265 / FeedForward
     :374-391 inside the pre-norm residual of :286 / :477).  HIP forward; backward = HIP depthwise / gate /
@@ -394,7 +402,7 @@ class _GdfnRes(torch.autograd.Function):
         B, H, W = geom
         pf = ffn.packed(a2.dtype)
         D, HP = a2.shape[1], pf["w_out"].shape[1]
-        if B * H * W >= ops.GDFN_FUSED_MIN_PIXELS and ops.gdfn_fused_fits(D, HP, H, W, a2.dtype):
+        if _gdfn_fuses(B, H, W, D, HP, a2.dtype):
             # one launch; t (what the backward needs) is written, the gate product never reaches HBM
             y, t = ops.gdfn_fused(a2, ln.pair(), pf["w_in"], pf["w9"], pf["w_out"], B, H, W, keep=True)
         else:
@@ -433,14 +441,16 @@ class _GdfnRes(torch.autograd.Function):
 
 def _gdfn_res_ag(ffn, ln, a2, B, H, W):
     if not torch.is_grad_enabled():
-        # no_grad: the whole block in one launch where the fused kernel covers the shape and the image is big enough to fill
-        # the chip with its pixel tiles (t = project_in(LN(a)) and the gate product never reach HBM)
+        # no_grad: the whole block in one launch where it applies (t = project_in(LN(a)) and the gate product never reach HBM)
         pf = ffn.packed(a2.dtype)
-        D, HP = a2.shape[1], pf["w_out"].shape[1]
-        if B * H * W >= ops.GDFN_FUSED_MIN_PIXELS and ops.gdfn_fused_fits(D, HP, H, W, a2.dtype):
+        if _gdfn_fuses(B, H, W, a2.shape[1], pf["w_out"].shape[1], a2.dtype):
             return ops.gdfn_fused(a2, ln.pair(), pf["w_in"], pf["w9"], pf["w_out"], B, H, W)
     return _GdfnRes.apply(ffn, ln, (B, H, W), a2, ln.body.weight, ln.body.bias, ffn.project_in.weight, ffn.dwconv.weight,
                           ffn.project_out.weight)
+
+
+# what _SelfChannelAttnRes keeps for its backward (t: the 1x1-conv output; qk: None where pass A could not emit it)
+_SelfAttnSaved = namedtuple("_SelfAttnSaved", "t2 t v gp sp MbT qk")
 
 
 class _SelfChannelAttnRes(torch.autograd.Function):
@@ -452,47 +462,31 @@ class _SelfChannelAttnRes(torch.autograd.Function):
         D = t2.shape[1]
         dt = t2.dtype
         pa = attn.packed(dt)
-        w9 = pa["w9"]
-        if ops.FUSED_TRAIN and ops.qkv_dwconv_gram_fits(D, attn.num_heads, H, W, dt):
-            v, gp, sp, _, q, qk = ops.qkv_dwconv_gram(t2, pa["wqkv"], w9, B, H, W, D, attn.num_heads, ln=ln.pair(), keep=True)
-        else:
-            q = ops.gemm_tok(t2, pa["wqkv"], ln=ln.pair())
-            v, gp, sp, _, qk = ops.dwconv_gram(q[:, :D], q[:, D:2 * D], q[:, 2 * D:], w9[:, :D], w9[:, D:2 * D], w9[:, 2 * D:], 3 * D,
-                                               B, H, W, D, attn.num_heads, keep_qk=True)
+        v, gp, sp, t, qk = _pass_a(t2, pa["wqkv"], pa["w9"], B, H, W, D, attn.num_heads, ln=ln.pair(), keep=True)
         Mb, MbT, gp, sp = ops.spectral_fold(gp, sp, pa["temp"], pa["wo"], dt, transposed=True)
         a = ops.gemm_tok(v, Mb, epi=1, res=t2)
         ctx.attn, ctx.ln, ctx.geom = attn, ln, geom
-        ctx.has_qk = qk is not None
-        ctx.save_for_backward(t2, q, v, gp, sp, Mb, MbT, *([qk] if qk is not None else []))
+        ctx.save_for_backward(*_SelfAttnSaved(t2, t, v, gp, sp, MbT, qk))
         return a
 
     @staticmethod
     def backward(ctx, da):
-        t2, q, v, gp, sp, Mb, MbT = ctx.saved_tensors[:7]
-        qk = ctx.saved_tensors[7] if ctx.has_qk else None
+        s = _SelfAttnSaved(*ctx.saved_tensors)
+        t2 = s.t2
         attn, ln, (B, H, W) = ctx.attn, ctx.ln, ctx.geom
-        D = t2.shape[1]
-        M = t2.shape[0]
+        M, D = t2.shape
         pa = attn.packed(t2.dtype)
-        w9 = pa["w9"]
         da = da.contiguous()
-        q4 = q.reshape(B, H, W, 3 * D)
         with ops.reduce_scope(leaf=True):      # every split partial of this backward is summed by ONE launch when the scope exits
-            dtq, dtk, dtv, dwq, dwk, dwv, dtemp, dwo = channel_attention_bwd(
-                da, q4[..., :D], q4[..., D:2 * D], q4[..., 2 * D:], w9[:, :D], w9[:, D:2 * D], w9[:, 2 * D:], v, gp, sp, Mb, MbT,
-                attn.temperature, attn.project_out.weight, attn.num_heads, B, H, W, qk=qk)
-            if dtq.data_ptr() + D * dtq.element_size() == dtk.data_ptr() and dtq.stride(2) == 3 * D:
-                dt3 = torch.as_strided(dtq, (M, 3 * D), (3 * D, 1))
-            else:
-                dt3 = torch.cat([dtq, dtk, dtv], dim=-1).reshape(M, 3 * D)
+            dt3, d_dw, dtemp, dwo = channel_attention_bwd_self(da, s.t.reshape(B, H, W, 3 * D), pa["w9"], s.v, s.gp, s.sp, s.MbT,
+                                                               attn.temperature, attn.project_out.weight, attn.num_heads, qk=s.qk)
             lw, lb = ln.pair()
-            if ops.ln_bwd_win_dxn_fits(M, D, t2.dtype) and dt3.is_contiguous():      # the qkv conv's data gradient inside the LayerNorm-backward launch
+            if ops.ln_bwd_win_dxn_fits(M, D, t2.dtype):      # the qkv conv's data gradient inside the LayerNorm-backward launch
                 dt_in, dlw, dlb, xn = ops.ln_bwd_tok_dxn(t2, dt3, pa["wqkvT"], da, lw, lb)
             else:
                 dt_in, dlw, dlb, xn = ops.ln_bwd_tok(t2, ops.gemm_tok(dt3, pa["wqkvT"]), da, lw, lb)
             d_qkv = ops.gemm_tn(dt3, xn).reshape(3 * D, D, 1, 1)
-        d_dw = _join_taps(dwq, dwk, dwv).reshape(3 * D, 1, 3, 3)
-        return None, None, None, dt_in, dlw, dlb, d_qkv, d_dw, dwo.reshape(D, D, 1, 1), dtemp.reshape(-1, 1, 1)
+        return None, None, None, dt_in, dlw, dlb, d_qkv, d_dw.reshape(3 * D, 1, 3, 3), dwo.reshape(D, D, 1, 1), dtemp.reshape(-1, 1, 1)
 
 
 class _CrossChannelAttnRes(torch.autograd.Function):
@@ -524,29 +518,22 @@ class _CrossChannelAttnRes(torch.autograd.Function):
         Mb, MbT, gp, sp = ops.spectral_fold(gp, sp, pa["temp"], pa["wo"], dt, transposed=True)
         a = ops.gemm_tok(v, Mb, epi=1, res=text_c)
         ctx.ct, ctx.geom = ct, geom
-        ctx.save_for_backward(text32, vis1, xq, tq, tkv, v, gp, sp, Mb, MbT, vis1_f32)
+        ctx.save_for_backward(text32, vis1, xq, tq, tkv, v, gp, sp, MbT, vis1_f32)
         return a
 
     @staticmethod
     def backward(ctx, da):
-        text32, vis1, xq, tq, tkv, v, gp, sp, Mb, MbT, vis1_f32 = ctx.saved_tensors
+        text32, vis1, xq, tq, tkv, v, gp, sp, MbT, vis1_f32 = ctx.saved_tensors
         ct, (B, H, W) = ctx.ct, ctx.geom
         attn = ct.attn
         D = text32.shape[1]
         M = text32.shape[0]
         pa = attn.packed(vis1.dtype)
-        w9 = pa["w9"]
         da = da.contiguous()
-        tq4, tkv4 = tq.reshape(B, H, W, D), tkv.reshape(B, H, W, 2 * D)
         with ops.reduce_scope(leaf=True):      # every split partial of this backward is summed by ONE launch when the scope exits
-            dtq, dtk, dtv, dwq, dwk, dwv, dtemp, dwo = channel_attention_bwd(
-                da, tq4, tkv4[..., :D], tkv4[..., D:], w9[:, :D], w9[:, D:2 * D], w9[:, 2 * D:], v, gp, sp, Mb, MbT,
-                attn.temperature, attn.project_out.weight, attn.num_heads, B, H, W)
-            dtq2 = dtq.reshape(M, D).contiguous()
-            if dtk.data_ptr() + D * dtk.element_size() == dtv.data_ptr() and dtk.stride(2) == 2 * D:      # halves of one buffer
-                dkv = torch.as_strided(dtk, (M, 2 * D), (2 * D, 1))
-            else:
-                dkv = torch.cat([dtk, dtv], dim=-1).reshape(M, 2 * D)
+            dtq, dkv, d_dw, dtemp, dwo = channel_attention_bwd_cross(da, tq.reshape(B, H, W, D), tkv.reshape(B, H, W, 2 * D), pa["w9"], v, gp, sp, MbT,
+                                                                     attn.temperature, attn.project_out.weight, attn.num_heads)
+            dtq2 = dtq.reshape(M, D)
             n11w, n11b = ct.norm11.pair()
             n12w, n12b = ct.norm12.pair()
             # norm11 backward in fp32 on the fp32 text map (see the class docstring); dres = the residual path of `a`.  Where the kernel covers
@@ -568,8 +555,8 @@ class _CrossChannelAttnRes(torch.autograd.Function):
             d_wq = ops.gemm_tn(dtq2, xq).reshape(D, D, 1, 1)
             d_wkv = ops.gemm_tn(dkv1, xv).reshape(2 * D, D, 1, 1)
         d_prompt = dvis.t().reshape(1, D, H, W)               # (ps*ps, D) tokens -> the parameter's (1, D, ps, ps), a view
-        return (None, None, None, dtext, None, None, d_prompt, d11w, d11b, d12w, d12b, d_wq, d_wkv, dwq.reshape(D, 1, 3, 3),
-                _join_taps(dwk, dwv).reshape(2 * D, 1, 3, 3), dwo.reshape(D, D, 1, 1), dtemp.reshape(-1, 1, 1))
+        return (None, None, None, dtext, None, None, d_prompt, d11w, d11b, d12w, d12b, d_wq, d_wkv, d_dw[:D].reshape(D, 1, 3, 3),
+                d_dw[D:].reshape(2 * D, 1, 3, 3), dwo.reshape(D, D, 1, 1), dtemp.reshape(-1, 1, 1))
 
 
 class _TextMap(torch.autograd.Function):
@@ -621,7 +608,9 @@ def tvsp(mod, x, clip_prompt, prompt_weights, out=None):
 
 class _JoinLeft(torch.autograd.Function):
     """cat([x, p], -1) where p already IS the right half of `buf` (TVSP's last conv wrote it there): x is copied into the left half and the
-    buffer is the result -- half the bytes of the cat launch (ref :596)."""
+    buffer is the result -- half the bytes of the cat launch (ref :596).
+    Invariant (enforced nowhere): p is a view of the buffer this forward writes in place, so p must not be consumed or saved anywhere
+    except by this join -- any other autograd use of it fails ("... is a view and its base ... has been modified inplace")."""
 
     @staticmethod
     def forward(ctx, x, p, buf):
@@ -672,14 +661,6 @@ def _packed_conv3x3(conv, w, dtype):
                                                            bwd=ops.pack_conv3x3(w, dtype, flip_transpose=True)))
 
 
-def _row_major(t):
-    """a 2-D view the token kernels can read as it is (unit column stride, 16-byte aligned rows), else one contiguous copy"""
-    es = t.element_size()
-    if t.dim() == 2 and t.stride(1) == 1 and (t.stride(0) * es) % 16 == 0 and t.data_ptr() % 16 == 0 and t.stride(0) >= t.shape[1]:
-        return t
-    return t.contiguous()
-
-
 class _Conv1x1(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, conv, out=None):
@@ -699,7 +680,7 @@ class _Conv1x1(torch.autograd.Function):
         N, K = w.shape[0], w.shape[1]
         dy2, x2 = dy.reshape(-1, N), x.reshape(-1, K)
         pk = _packed_conv1x1(ctx.conv, w, x.dtype)
-        dy2 = _row_major(dy2)            # a channel slice of a wider gradient (the split of a `cat`) is read in place through its row pitch
+        dy2 = ops.row_major(dy2)           # a channel slice of a wider gradient (the split of a `cat`) is read in place through its row pitch
         dx = None
         if ctx.needs_input_grad[0]:
             dx = ops.gemm_tok(dy2, pk["wT"]).reshape(x.shape)
@@ -711,7 +692,9 @@ class _Conv1x1(torch.autograd.Function):
 
 
 def conv1x1(x, conv, out=None):
-    """bias-free 1x1 conv / Linear on channels-last data; `conv` is the nn.Conv2d holder (its packed weights are cached on it)."""
+    """bias-free 1x1 conv / Linear on channels-last data; `conv` is the nn.Conv2d holder (its packed weights are cached on it).
+    out: a channel slice of a joint buffer the result is written into.  The result then is a view of that buffer, which the join
+    (_JoinLeft / shuffle_join) goes on to write in place: it must not be consumed or saved anywhere except by that join."""
     return _Conv1x1.apply(x, conv.weight, conv, out)
 
 
@@ -761,7 +744,8 @@ class _Conv3x3(torch.autograd.Function):
 
 
 def conv3x3(x, conv, keep_pad=False, out=None):
-    """dense 3x3, stride 1, zero padding, no bias on channels-last data; `conv` is the nn.Conv2d holder."""
+    """dense 3x3, stride 1, zero padding, no bias on channels-last data; `conv` is the nn.Conv2d holder.
+    out: as for conv1x1 -- the result must not be consumed or saved anywhere except by the join that completes its buffer."""
     return _Conv3x3.apply(x, conv.weight, conv, keep_pad, out)
 
 
@@ -837,7 +821,8 @@ def pixel_unshuffle2(x):
 
 class _ShuffleJoin(torch.autograd.Function):
     """cat([pixel_shuffle2(c), f], -1) where f already IS the right half of `buf` (its producer wrote it there through the row pitch):
-    the shuffle writes the left half and the buffer is the result -- no cat launch, the decoder's concatenations (ref :838, :843)."""
+    the shuffle writes the left half and the buffer is the result -- no cat launch, the decoder's concatenations (ref :838, :843).
+    Invariant (enforced nowhere): as for _JoinLeft, f must not be consumed or saved anywhere except by this join."""
 
     @staticmethod
     def forward(ctx, c, f, buf):

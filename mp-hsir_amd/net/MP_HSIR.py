@@ -188,7 +188,7 @@ class PGSSTB(nn.Module):                                                        
 
     def forward(self, x, text_prompt=None, res=None, skip=None):
         """x: channels-last (B,H,W,C) in the compute dtype; res: a second residual added to the output by the last launch;
-        skip: (AG.SkipGrad, is first block, is last block) of the enclosing BaseBlock, see there"""
+        skip: AG.Skip(holder, first, last) -- the AG.SkipGrad of the enclosing BaseBlock and this block's place in it, see there"""
         k1, k2 = self.drop_path_factors(x.shape[0], x.device)
         return AG.pgsstb(self, x, k1, k2, res, skip)
 
@@ -215,7 +215,7 @@ class BaseBlock(nn.Module):                                                     
         hold = AG.SkipGrad() if (ops.BASE_SKIP_BWD and torch.is_grad_enabled() and x.requires_grad) else None
         for i, blk in enumerate(self.blocks):
             y = blk(y, res=x if i == n - 1 else None,           # the skip `+ x` (ref :760) rides in the last block's gated-MLP launch
-                    skip=None if hold is None else (hold, i == 0, i == n - 1))
+                    skip=None if hold is None else AG.Skip(holder=hold, first=i == 0, last=i == n - 1))
         return y
 
 

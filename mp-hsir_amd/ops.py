@@ -471,24 +471,28 @@ class MultiCopy:
         _acct("multi_copy", 0.0, 8.0 * sum(d.numel() for d in dsts))
 
 
+def _l1_clamp_loss_launch(y, clean, want_grad):
+    """one launch: -> (mean |clamp(y, 0, 1) - clean| as a 0-d tensor, its gradient w.r.t. y or None)"""
+    lib = _lib.load()
+    _check(y, clean)
+    y, clean = y.contiguous(), clean.contiguous()
+    assert y.dtype == torch.float32 and clean.dtype == torch.float32 and y.shape == clean.shape
+    n = y.numel()
+    nblk = max(1, min(1024, (n + 1023) // 1024))
+    g = torch.empty_like(y) if want_grad else None
+    part = torch.empty((nblk, 1), dtype=torch.float32, device=y.device)
+    _lib.check(lib.mphsir_l1_clamp_loss(_p(y), _p(clean), _p(g), _p(part), n, nblk, _stream(y)), "l1_clamp_loss")
+    _acct("l1_clamp_loss", 4.0 * n, 4.0 * n * (3 if want_grad else 2))
+    return reduce_parts(part, immediate=True).reshape(()), g
+
+
 class _L1ClampLoss(torch.autograd.Function):
     """mean |clamp(y, 0, 1) - clean| with its gradient from the same pass (mphsir_l1_clamp_loss; train.py:58-61)"""
 
     @staticmethod
     def forward(ctx, y, clean):
-        lib = _lib.load()
-        _check(y, clean)
-        y, clean = y.contiguous(), clean.contiguous()
-        assert y.dtype == torch.float32 and clean.dtype == torch.float32 and y.shape == clean.shape
-        n = y.numel()
-        nblk = max(1, min(1024, (n + 1023) // 1024))
-        need = ctx.needs_input_grad[0]
-        g = torch.empty_like(y) if need else None
-        part = torch.empty((nblk, 1), dtype=torch.float32, device=y.device)
-        _lib.check(lib.mphsir_l1_clamp_loss(_p(y), _p(clean), _p(g), _p(part), n, nblk, _stream(y)), "l1_clamp_loss")
-        _acct("l1_clamp_loss", 4.0 * n, 4.0 * n * (3 if need else 2))
-        ctx.g = g
-        return reduce_parts(part, immediate=True).reshape(())
+        loss, ctx.g = _l1_clamp_loss_launch(y, clean, ctx.needs_input_grad[0])
+        return loss
 
     @staticmethod
     def backward(ctx, dloss):
@@ -504,17 +508,7 @@ def l1_clamp_loss(y, clean):
 def l1_clamp_loss_grad(y, clean):
     """(mean |clamp(y, 0, 1) - clean|, its gradient w.r.t. y) from one pass, outside autograd: for a caller that starts the backward pass
     at y itself (engine.DataParallelEngine: `y.backward(g)` instead of `loss.backward()`, whose ones_like + scale launches it saves)"""
-    lib = _lib.load()
-    _check(y, clean)
-    y, clean = y.contiguous(), clean.contiguous()
-    assert y.dtype == torch.float32 and clean.dtype == torch.float32 and y.shape == clean.shape
-    n = y.numel()
-    nblk = max(1, min(1024, (n + 1023) // 1024))
-    g = torch.empty_like(y)
-    part = torch.empty((nblk, 1), dtype=torch.float32, device=y.device)
-    _lib.check(lib.mphsir_l1_clamp_loss(_p(y), _p(clean), _p(g), _p(part), n, nblk, _stream(y)), "l1_clamp_loss")
-    _acct("l1_clamp_loss", 4.0 * n, 12.0 * n)
-    return reduce_parts(part, immediate=True).reshape(()), g
+    return _l1_clamp_loss_launch(y, clean, True)
 
 
 def _rows(t):
@@ -562,9 +556,6 @@ def gemm_tok(x, w, bias=None, ln=None, epi=0, res=None, sa=None, gate=None, keep
     es = x.element_size()
     _acct("gemm_tok", 2.0 * M * N * K, (M * K + M * N * (1 + (res is not None) + (sa is not None))) * es + w.numel() * es)
     return y
-
-
-
 
 
 def layernorm_tok(x, ln_w, ln_b, out_dtype, want_cast=False):
@@ -1905,6 +1896,14 @@ def pixel_pitch(t):
     ld = t.stride(2)
     ok = t.stride(3) == 1 and ld >= C and t.stride(1) == W * ld and t.stride(0) == H * W * ld and (ld * t.element_size()) % 16 == 0 and t.data_ptr() % 16 == 0
     return ld if ok else None
+
+
+def row_major(t):
+    """the 2-D twin of pixel_pitch: a view the token kernels can read as it is (unit column stride, 16-byte aligned rows), else one contiguous copy"""
+    es = t.element_size()
+    if t.dim() == 2 and t.stride(1) == 1 and (t.stride(0) * es) % 16 == 0 and t.data_ptr() % 16 == 0 and t.stride(0) >= t.shape[1]:
+        return t
+    return t.contiguous()
 
 
 def conv3x3_tok(x, wp, out=None):

@@ -1205,9 +1205,18 @@ def check_channel_attention_bwd(dev, dtype, C, heads, shape, cross=False):
     Mb, MbT, gp, sp = ops.spectral_fold(gp, sp, temp, wo, dtype, transposed=True)
     out = ops.gemm_tok(v, Mb)
     with ops.reduce_scope():
-        dtq, dtk, dtv, dwq, dwk, dwv, dtemp, dwo = AG.channel_attention_bwd(
-            d_out, views[0], views[1], views[2], w9[:, :C], w9[:, C:2 * C], w9[:, 2 * C:], v, gp, sp, Mb, MbT,
-            P["temperature"], P["project_out.weight"], heads, B, H, W)
+        if cross:
+            dtq, dkv, dw, dtemp, dwo = AG.channel_attention_bwd_cross(d_out, tq4, tkv4, w9, v, gp, sp, MbT, P["temperature"], P["project_out.weight"], heads)
+            assert dtq.shape == (B, H, W, C) and dkv.shape == (M, 2 * C)
+            dkv4 = dkv.reshape(B, H, W, 2 * C)
+            dtk, dtv = dkv4[..., :C], dkv4[..., C:]
+        else:
+            dt_all, dw, dtemp, dwo = AG.channel_attention_bwd_self(d_out, t4, w9, v, gp, sp, MbT, P["temperature"], P["project_out.weight"], heads)
+            assert dt_all.shape == (M, 3 * C)
+            dt4 = dt_all.reshape(B, H, W, 3 * C)
+            dtq, dtk, dtv = dt4[..., :C], dt4[..., C:2 * C], dt4[..., 2 * C:]
+    assert dw.shape == (3 * C, 9) and dw.dtype == torch.float32
+    dwq, dwk, dwv = dw[:C], dw[C:2 * C], dw[2 * C:]            # the per-tensor gradients: slices of the joined buffers the entry points return
     # oracle on the 1x1-conv outputs as the kernels saw them (dtype-rounded), fp64 from there on
     tqd = views[0].detach().double().cpu().requires_grad_(True)
     tkd = views[1].detach().double().cpu().requires_grad_(True)
@@ -1231,6 +1240,70 @@ def check_channel_attention_bwd(dev, dtype, C, heads, shape, cross=False):
     bad = {n: e for n, e in errs.items() if not e < tol}
     assert not bad, (C, heads, shape, str(dtype), bad)
     return errs
+
+
+def check_channel_attention_bwd_refuses_layouts(dev, dtype=torch.float32, C=64, heads=2, shape=(1, 16, 16)):
+    """The self entry point declares its layouts -- t one contiguous (B,H,W,3C), w9 one contiguous fp32 (9,3C) -- and raises on anything
+    else BEFORE any launch: there is no slower path to fall to."""
+    _use(dev)
+    from mp_hsir_amd import autograd_ops as AG
+    from mp_hsir_amd import ops
+    B, H, W = shape
+    M, hd = B * H * W, C // heads
+    d_out, v = rnd((M, C), 341, dtype), rnd((M, C), 342, dtype)
+    gp, sp = rnd((B, 1, heads, hd, hd), 343), rnd((B, 1, 2, C), 344).abs() + 1
+    MbT = rnd((B, C, C), 345, dtype, scale=C ** -0.5)
+    temp, wo = 1 + 0.3 * rnd((heads, 1, 1), 346), rnd((C, C, 1, 1), 347, scale=C ** -0.5)
+    t, w9 = rnd((B, H, W, 3 * C), 348, dtype), rnd((9, 3 * C), 349, scale=1 / 3)
+    wide_t, wide_w9 = rnd((B, H, W, 4 * C), 350, dtype), rnd((9, 4 * C), 351, scale=1 / 3)
+    bad = {"t: pitch 4C": (wide_t[..., :3 * C], w9),
+           "t: (M,3C)": (t.reshape(M, 3 * C), w9),
+           "w9: pitch 4C": (t, wide_w9[:, :3 * C]),
+           "w9: (3C,9) transposed": (t, rnd((3 * C, 9), 352, scale=1 / 3).t()),
+           "w9: not fp32": (t, w9.to(torch.float64))}
+    for what, (t_, w9_) in bad.items():
+        ops.ACCOUNT = {}
+        try:
+            try:
+                AG.channel_attention_bwd_self(d_out, t_, w9_, v, gp, sp, MbT, temp, wo, heads)
+            except AssertionError as e:
+                assert "stride" in str(e) and str(tuple(t_.shape if what[0] == "t" else w9_.shape)) in str(e), (what, str(e))
+            else:
+                raise RuntimeError("channel_attention_bwd_self accepted " + what)
+            assert not ops.ACCOUNT, (what, "launched before refusing", sorted(ops.ACCOUNT))
+        finally:
+            ops.ACCOUNT = None
+
+
+def check_join_gradients(dev, shape=(1, 8, 16), C=32):
+    """The joins that complete a buffer whose right half its producer already wrote (conv1x1(out=) -> _JoinLeft, conv3x3(out=) ->
+    shuffle_join) against the same producers followed by torch.cat / pixel_shuffle2, fp32: the output and the gradients of both halves'
+    inputs and of the conv weight, bit for bit (the same kernels on the same values: only the row pitch they go through differs)."""
+    _use(dev)
+    from mp_hsir_amd import autograd_ops as AG
+    B, H, W = shape
+    cot = rnd((B, H, W, 2 * C), 366)
+
+    def run(left, ksize, joined):
+        conv = torch.nn.Conv2d(C, C, ksize, padding=ksize // 2, bias=False).to(dev)
+        with torch.no_grad():
+            conv.weight.copy_(rnd(conv.weight.shape, 361, scale=(C * ksize * ksize) ** -0.5))
+        produce = AG.conv1x1 if ksize == 1 else AG.conv3x3
+        lshape = (B, H, W, C) if left == "plain" else (B, H // 2, W // 2, 4 * C)
+        x, yin = rnd(lshape, 362).requires_grad_(True), rnd((B, H, W, C), 363).requires_grad_(True)
+        if joined:
+            buf = torch.empty((B, H, W, 2 * C), dtype=torch.float32, device=dev)
+            p = produce(yin, conv, out=buf[..., C:])
+            j = AG._JoinLeft.apply(x, p, buf) if left == "plain" else AG.shuffle_join(x, p, buf)
+        else:
+            j = torch.cat([x if left == "plain" else AG.pixel_shuffle2(x), produce(yin, conv)], dim=-1)
+        (j * cot).sum().backward()
+        return j.detach(), x.grad, yin.grad, conv.weight.grad
+
+    for left, ksize in (("plain", 1), ("shuffled", 3), ("shuffled", 1)):
+        got, want = run(left, ksize, True), run(left, ksize, False)
+        for name, g, w in zip(("out", "d left", "d producer input", "d conv weight"), got, want):
+            assert g is not None and g.shape == w.shape and torch.equal(g, w), (left, ksize, name, rel_l2(g, w))
 
 
 def check_loss_scaler(dev):

@@ -522,6 +522,60 @@ def check_fused_block_equals_unfused(dev, name="nat_enc1", dtype=torch.bfloat16)
         assert torch.equal(g0[k], g1[k]), k
 
 
+def check_base_skip_bwd(dev, depth, dtype=torch.float32, fuse=False, shape=(1, 16, 16), C=64):
+    """A BaseBlock's gradients with the skip gradient handed from the last block's backward to the first block's (ops.BASE_SKIP_BWD,
+    autograd_ops.SkipGrad) against autograd summing the two gradients of x itself: every launch but the one that forms dx of the first
+    block is the same, so every parameter gradient is bit for bit the same; dx differs by where its third term is added and is held to
+    the block-gradient bars (fp32: check_block_gradients' 2e-4, bf16: kernel_checks.TOL).  The holder is empty after each backward.
+    fuse: the blocks run as _Pgsstb (16-bit types) instead of _PgsstbAttn + _GatedMlp."""
+    from golden.detfill import det_value
+    from kernel_checks import TOL
+    from mp_hsir_amd import autograd_ops as AG
+    from mp_hsir_amd import ops
+    from mp_hsir_amd.net.MP_HSIR import BaseBlock
+    B, H, W = shape
+    mod = BaseBlock(C, 8, (64, 64), depth, 2, 2.66, 8, 128, drop_path=[0.0] * depth).eval()
+    with torch.no_grad():
+        for k, p in mod.named_parameters():
+            p.copy_(det_value(k, p.shape).float())
+    mod = mod.to(dev)
+    x0 = seeded_input("skip_bwd:x", (B, C, H, W), "normal").to(dev).permute(0, 2, 3, 1).contiguous().to(dtype)
+    cot = seeded_input("skip_bwd:cot", (B, C, H, W), "normal").to(dev).permute(0, 2, 3, 1).to(dtype)
+    holders = []
+
+    class Recorded(AG.SkipGrad):
+        def __init__(self):
+            super().__init__()
+            holders.append(self)
+
+    saved = (ops.BASE_SKIP_BWD, ops.MLP_FUSE_SUM, ops.MLP_FUSE_MIN_TILES, AG.SkipGrad)
+    res = {}
+    try:
+        AG.SkipGrad = Recorded
+        ops.MLP_FUSE_SUM, ops.MLP_FUSE_MIN_TILES = fuse, 1
+        assert ops.gated_mlp_fuses(B * H * W, C, H * W, dtype) == fuse
+        for on in (True, False):
+            ops.BASE_SKIP_BWD = on
+            del holders[:]
+            mod.zero_grad(set_to_none=True)
+            x = x0.clone().requires_grad_(True)
+            y = mod(x)
+            (y * cot).sum().backward()
+            assert len(holders) == (1 if on else 0), (on, len(holders))
+            assert all(h.dz is None for h in holders), "the skip gradient was left in its holder"
+            res[on] = (y.detach(), x.grad, {k: p.grad.clone() for k, p in mod.named_parameters()})
+    finally:
+        ops.BASE_SKIP_BWD, ops.MLP_FUSE_SUM, ops.MLP_FUSE_MIN_TILES, AG.SkipGrad = saved
+    (y1, dx1, g1), (y0, dx0, g0) = res[True], res[False]
+    assert torch.equal(y1, y0)
+    for k in g0:
+        assert torch.equal(g1[k], g0[k]), (k, rel_l2(g1[k], g0[k]))
+    e = rel_l2(dx1, dx0)
+    print("skip gradient on/off: depth %d %s fuse=%s: dx rel-L2 %.3g" % (depth, dtype, fuse, e))
+    assert e < (2e-4 if dtype == torch.float32 else TOL[dtype]), (depth, str(dtype), fuse, e)
+    return e
+
+
 def check_pack_plan(dev, dtype=torch.float32, steps=3):
     """engine.PackPlan (all kernel-layout weights = one gather from the flat arena) against the per-module packers:
     every module cache gets pinned, and the parameter trajectory of a few AdamW steps is bitwise the same."""

@@ -245,6 +245,14 @@ def test_spectral_dqkv_bwd_against_the_three_launches(dtype, C, heads, shape):
     print(K.check_spectral_dqkv_bwd("cpu", dtype, C, heads, shape))
 
 
+def test_channel_attention_bwd_self_refuses_other_layouts():
+    K.check_channel_attention_bwd_refuses_layouts("cpu")
+
+
+def test_gradients_through_the_joins():
+    K.check_join_gradients("cpu")
+
+
 def test_channel_attention_bwd_self_16bit_takes_the_fused_launch():
     from mp_hsir_amd import ops
     ops.ACCOUNT = {}

@@ -40,6 +40,14 @@ def test_fused_block_equals_unfused_bf16():
     M.check_fused_block_equals_unfused("cpu", "nat_enc1")
 
 
+@pytest.mark.parametrize("depth", [1, 2])
+@pytest.mark.parametrize("dtype,fuse", [("float32", False), ("bfloat16", False), ("bfloat16", True)])
+def test_base_block_skip_gradient_on_equals_off(depth, dtype, fuse):
+    """the BaseBlock skip gradient through autograd_ops.SkipGrad against autograd's own sum: _PgsstbAttn + _GatedMlp and _Pgsstb"""
+    import torch
+    M.check_base_skip_bwd("cpu", depth, getattr(torch, dtype), fuse)
+
+
 def test_pack_plan_matches_per_module_packers():
     import torch
     M.check_pack_plan("cpu")

@@ -101,6 +101,14 @@ def test_fused_block_equals_unfused(name, dtype):
     M.check_fused_block_equals_unfused("cuda", name, dtype)
 
 
+@pytest.mark.parametrize("depth", [1, 2])
+@pytest.mark.parametrize("dtype,fuse", [(torch.float32, False), (torch.bfloat16, False), (torch.bfloat16, True)])
+def test_base_block_skip_gradient_on_equals_off(depth, dtype, fuse):
+    """the BaseBlock skip gradient through autograd_ops.SkipGrad against autograd's own sum: every parameter gradient bit for bit, dx
+    within the block-gradient bars, the holder empty after each backward"""
+    M.check_base_skip_bwd("cuda", depth, dtype, fuse)
+
+
 @pytest.mark.parametrize("name", list(BLOCK_CASES))
 def test_block_gradients_fp32(name):
     """every shape class of both shipped configurations (C 64..384, head_dim 32..96) + TVSP + PromptFusion: output, dX and
