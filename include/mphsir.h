@@ -725,6 +725,26 @@ typedef struct mphsir_degrade_args {
 } mphsir_degrade_args;
 int mphsir_degrade_batch(const mphsir_degrade_args* a, void* stream);
 
+/* ---- the same degradation for planes of ANY size: whole cubes (evaluation), training patches beyond 128 x 128 ----------------------------
+ * The tiled form of mphsir_degrade_batch: one workgroup per 64 x 64 output tile of a (sample, band) plane (right and bottom tiles
+ * partial), the source tile staged in LDS with a halo of k / 2 that holds the real neighbours inside the plane and zero outside it.  The
+ * same struct, the same plan, kinds, draws and element values; no atomics, no temporary in HBM, one launch.  What differs:
+ *   H and W are arbitrary (W % 4 != 0 included: dwordx4 loads / stores are used when W % 4 == 0 and the three cubes are 16-byte
+ *     aligned, scalar ones otherwise); col_dead, col_off are [B][C][W], cirrus is [B][H][W], the draws [B][C][H][W].
+ *   clean_aug may be NULL: the copy is not written at all.
+ *   aug may be NULL: mode 0 for every sample.  With H != W aug MUST be NULL (no flips / rotations of non-square planes); with H == W
+ *     all eight modes work as in mphsir_degrade_batch.
+ *   sr_factor: f >= 1 divides H and W, H / f >= 2 and W / f >= 2.  The low-resolution image is (H / f) x (W / f), its pixels at the
+ *     align_corners coordinates of the WHOLE plane, (H - 1) / (H / f - 1) and (W - 1) / (W / f - 1) in fp32: no value depends on the tiles.
+ *   Generated draws: the element's linear index in the un-augmented [B][C][H][W] cube is the counter, as before.
+ * Guarantee: for H == W = N, N * N <= 128 * 128 and the same plan, seed, ordinal and draws, `degraded` and `clean_aug` are BITWISE those
+ *   of mphsir_degrade_batch, for every kind and every mode.
+ * MPHSIR_EINVAL: aug != NULL with H != W, an even or too large stencil, a factor that does not divide H and W or leaves fewer than two
+ *   low-resolution rows / columns, an unknown kind, one or two of z / u0 / u1, a table missing that a kind of the menu reads,
+ *   B * C >= 2^31, H * W >= 2^31, B * C * tiles >= 2^31 (tiles = ceil(H / 64) * ceil(W / 64)).  Element indices are 64-bit.
+ *   LDS: 27.9 + 4 KiB with a 21 x 21 stencil and sr by 2 in the plan (five workgroups per CU), 16.3 KiB without a blur in the menu.  */
+int mphsir_degrade_planes(const mphsir_degrade_args* a, void* stream);
+
 /* ---- training patches cut out of a resident scene store: gather + per-patch min-max normalisation, one launch pair ------------------------
  * The store (mp-hsir_amd/scene_store.py) keeps every level of every scene in ONE fp32 arena: level l is a contiguous [C][H_l][W_l] cube
  * at element offset off_l.  A batch is B records (level, y, x): the C x P x P window p of the level with its top-left corner at (y, x).

@@ -279,6 +279,7 @@ _SYMBOLS = {
     "mphsir_quality_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "mphsir_quality": (c_int, [ctypes.POINTER(QualityArgs), c_void_p]),
     "mphsir_degrade_batch": (c_int, [ctypes.POINTER(DegradeArgs), c_void_p]),
+    "mphsir_degrade_planes": (c_int, [ctypes.POINTER(DegradeArgs), c_void_p]),
     "mphsir_patch_sample_workspace_bytes": (c_int64, [c_int32, c_int32]),
     "mphsir_patch_sample": (c_int, [ctypes.POINTER(PatchSampleArgs), c_void_p]),
     "mphsir_l1_clamp_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),

@@ -15,7 +15,9 @@ same numpy calls to recover the draws they consumed, and stores (draws, output);
 All functions take and return (B,C,H,W) float32 cubes; per-sample draws carry a leading batch axis.  PyTorch device ops
 only (this is the loader side of the boundary, not the model hot path) -- except DegradationSynthesizer(fused=True), which builds a
 plan of small tables with batched tensor ops, without a host synchronisation, and degrades the batch in ONE HIP launch
-(csrc/degrade.hip, ops.degrade_batch); the functions here stay the definition of every element value.  `file:line` = reference repository.
+(csrc/degrade.hip, ops.degrade_batch; ops.degrade_planes, the tiled form, for planes beyond 128 x 128), and SceneDegrader, which does
+the same for one whole cube under test.py's modes 0-10; the functions here stay the definition of every element value.
+`file:line` = reference repository.
 """
 import math
 
@@ -408,7 +410,10 @@ class DegradationSynthesizer:
         clean = clean.contiguous()
         plan, de_id = self.fused_plan(clean)
         self._ordinal += 1                                                               # the batch ordinal counts calls, on the device
-        degraded, clean_aug = ops.degrade_batch(clean, plan, seed=self.seed, ordinal=self._ordinal)
+        # planes that fit in LDS whole keep the plane form's launch; larger ones go through the tiled form, which computes the same values
+        H, W = clean.shape[-2:]
+        fn = ops.degrade_batch if H * W <= 128 * 128 else ops.degrade_planes
+        degraded, clean_aug = fn(clean, plan, seed=self.seed, ordinal=self._ordinal)
         return degraded, clean_aug, de_id.reshape(-1, 1)
 
     def __call__(self, clean):
@@ -424,3 +429,119 @@ class DegradationSynthesizer:
                 degraded[sel] = self.degrade_as(clean[sel], name)
         mode = self.d.randint(1, 8, (B,))                                                 # random.randint(1, 7)
         return augment(degraded, mode), augment(clean, mode), de_id.reshape(B, 1)
+
+
+class SceneDegrader:
+    """test.py's degradation modes 0-10 for one whole cube (1,C,H,W), any H and W, in ONE HIP launch (ops.degrade_planes): no cube-sized
+    temporary, no library convolution, and a result that depends on (seed, cube ordinal, the plan) only -- the per-element draws are the
+    launch's Philox draws keyed by the seed and the ordinal, which counts calls; the plan's small tables (per-band sigmas, band and column
+    subsets, the cirrus map) come from a seeded torch.Generator with the expressions of test.py::degrade_for_mode.  `opts`: test.py's
+    parsed flags.  Mode 11 (Poisson) has no fused form, mode 12 degrades nothing."""
+    PROMPT = {0: 0, 1: 1, 2: 1, 3: 1, 4: 1, 5: 2, 6: 0, 7: 3, 8: 4, 9: 5, 10: 5}
+
+    def __init__(self, model, device, seed):
+        self.model, self.device, self.seed = model, torch.device(device), int(seed)
+        self.d = Draws(device, seed)
+        self.ordinal = -1
+        self._stencils, self._haze_ratio, self._consts = {}, {}, {}
+
+    def prompt_id(self, mode):
+        return 6 if mode == 10 and self.model != "natural_scene" else self.PROMPT[mode]
+
+    def _const(self, shape, dtype, value, dev):
+        """a constant table, made once (the launch only reads its tables): a plan of mode 0 or 1 costs no fill launches"""
+        key = (tuple(shape), dtype, value)
+        if key not in self._consts:
+            self._consts[key] = torch.full(tuple(shape), value, dtype=dtype, device=dev)
+        return self._consts[key]
+
+    def _choice(self, values, n, dev):
+        """Draws.choice with the value list kept on the device (no host -> device copy per cube)"""
+        key = ("choice",) + tuple(values)
+        if key not in self._consts:
+            self._consts[key] = torch.tensor(values, dtype=torch.float32, device=dev)
+        return self._consts[key][self.d.randint(0, len(values), (n,))]
+
+    def _stencil(self, key, make):
+        if key not in self._stencils:
+            k = make()
+            st = torch.zeros((1, 21, 21), dtype=torch.float32)
+            if k.shape[-1] <= 21:
+                st[0, :k.shape[0], :k.shape[1]] = k
+            self._stencils[key] = (st.to(self.device), int(k.shape[-1]))               # a side beyond 21 (or even) is refused by the launch
+        return self._stencils[key]
+
+    def plan(self, clean, mode, opts):
+        """-> ops.DegradePlan for one cube: one task, mode 0 of the augmentation (aug=None), the tables of `mode`"""
+        from . import ops
+        d, o, dev = self.d, opts, clean.device
+        B, C, H, W = clean.shape
+        assert B == 1, "SceneDegrader degrades one cube per call"
+        if mode == 11:
+            raise ValueError("mode 11 is Poisson noise, which has no fused form (poissonN: distribution-level parity only)")
+        if mode not in self.PROMPT:
+            raise ValueError("SceneDegrader: modes 0-10, got %r" % (mode,))
+        nb = int(math.floor(C / 3))
+        f32 = lambda v: self._const((B,), torch.float32, float(v), dev)                  # noqa: E731
+        zero = lambda *shape, dt=torch.float32: self._const(shape, dt, 0, dev)           # noqa: E731
+        task, tabs = zero(B, dt=torch.int32), {}
+        kind, ksize, factors, param, sub = "none", [], [], 0.0, 0
+        if mode == 0:
+            kind, param = "gaussianN", f32(o.gaussian_noise_sigma / 255.0)
+        elif mode <= 4:
+            kind = "complexN"
+            sigmas = o.gaussian_noise_sigmas if mode == 1 else (10, 30, 50, 70)
+            tabs["band_sigma"] = self._choice([s / 255.0 for s in sigmas], B * C, dev).reshape(B, C)
+            flag, dead, off = zero(B, C, dt=torch.uint8), zero(B, C, W, dt=torch.uint8), zero(B, C, W)
+            if mode == 2:
+                lo, hi = o.stripe_nosie_ratio
+                bands = d.band_subset(B, C, nb)
+                n = d.randint(int(lo * W), max(int(hi * W), int(lo * W) + 1), (B, C))
+                cols = d.column_subsets(B, C, W, n) & bands[:, :, None]
+                off, sub = (d.rand(B, C, W) * 0.5 - 0.25) * cols, 2
+            elif mode == 3:
+                lo, hi = o.deadline_nosie_ratio
+                bands = d.band_subset(B, C, nb)
+                n = d.randint(int(math.ceil(lo * W)), max(int(math.ceil(hi * W)), int(math.ceil(lo * W)) + 1), (B, C))
+                dead = d.column_subsets(B, C, W, n) & bands[:, :, None]
+            elif mode == 4:
+                flag, sub = d.band_subset(B, C, nb), 1
+                param = self._choice(list(o.impulse_nosie_ratio), B, dev)
+            tabs.update(band_flag=flag.to(torch.uint8), col_dead=dead.to(torch.uint8), col_off=off.contiguous())
+        elif mode in (5, 6):
+            kind = "blur"
+            if mode == 5:
+                st, k = self._stencil(("gaussian", o.gaussian_blur_radius), lambda: gaussian_kernel2d(o.gaussian_blur_radius))
+            else:
+                st, k = self._stencil(("motion",) + tuple(o.motion_blur_radius), lambda: motion_kernel2d(*o.motion_blur_radius))
+            tabs["stencils"], ksize = st, [k]
+        elif mode == 7:
+            kind, factors = "sr", [int(o.downsample_factor)]
+        elif mode == 8:
+            kind, param = "inpaint", f32(o.mask_ratio)
+        elif mode == 9:
+            kind, param = "haze", f32(o.haze_omega)
+            low = d.rand(B, 1, max(H // 16, 2), max(W // 16, 2))
+            tabs["cirrus"] = F.interpolate(low, size=(H, W), mode="bilinear", align_corners=True)[:, 0].contiguous()
+            top_k = max(int(H * W * 0.01 / 100), 1)
+            flat = clean.reshape(B, C, -1)
+            tabs["atm"] = flat.amax(dim=-1) if top_k == 1 else flat.topk(top_k, dim=-1).values.mean(-1)
+            if C not in self._haze_ratio:
+                lam = torch.linspace(400, 1000, 100, device=dev, dtype=torch.float64)[:C]
+                self._haze_ratio[C] = (lam[0] / lam).to(torch.float32)
+            tabs["haze_ratio"] = self._haze_ratio[C]
+        else:
+            kind = "bandmiss"
+            n = int(o.bandmis_ratio * C)
+            tabs["band_flag"] = (d.rand(B, C).argsort(dim=1).argsort(dim=1) < n).to(torch.uint8)
+        param = param if torch.is_tensor(param) else f32(param)
+        return ops.DegradePlan([ops.DEG_KINDS[kind]], ksize, factors, task=task, aug=None, param=param.to(torch.float32).contiguous(),
+                               sub=self._const((B,), torch.int32, sub, dev), **tabs)
+
+    def __call__(self, clean, mode, opts):
+        """clean (1,C,H,W) fp32 on the device -> (degraded, prompt id): the plan, then one launch; no copy of the clean cube is written"""
+        from . import ops
+        clean = clean.contiguous()
+        plan = self.plan(clean, mode, opts)
+        self.ordinal += 1
+        return ops.degrade_planes(clean, plan, seed=self.seed, ordinal=self.ordinal, want_clean=False)[0], self.prompt_id(mode)

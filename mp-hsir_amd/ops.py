@@ -792,42 +792,59 @@ class DegradePlan:
             raise TypeError("DegradePlan: unknown tables %s" % sorted(tables))
 
 
-def degrade_batch(clean, plan, *, seed, ordinal, draws=None, out=None):
-    """clean (B,C,N,N) fp32, plan: a DegradePlan -> (degraded, clean_aug), each sample degraded by the kind of its task and both cubes under
-    its flip / rotation plan.aug (degrade.augment's modes), in ONE launch on the current stream.  draws = (z, u0, u1), three (B,C,N,N)
-    fp32 cubes read at the un-augmented element, or None: Philox4x32-10 draws from (seed, ordinal, element).  ordinal: an int, or a
-    one-element int64 tensor on the device that the launch itself reads (a captured launch replays with whatever it holds then).
-    out = (degraded, clean_aug) to write into."""
+def _degrade(fn, clean, plan, seed, ordinal, draws, out, want_clean=True):
+    """what degrade_batch and degrade_planes share: the checks of the cube, the plan's tables, the draws and the outputs, and the call.
+    out = (degraded, clean_aug | None)"""
     lib = _lib.load()
     tabs = [getattr(plan, n) for n, _, _ in _DEG_TABLES]
     dr = tuple(draws) if draws is not None else (None, None, None)
     od = ordinal if torch.is_tensor(ordinal) else None
     _check(clean, od, *tabs, *dr, *(out or ()))
-    assert clean.dim() == 4 and clean.dtype == torch.float32 and clean.is_contiguous(), "degrade_batch: a contiguous (B,C,N,N) fp32 batch"
+    assert clean.dim() == 4 and clean.dtype == torch.float32 and clean.is_contiguous(), "%s: a contiguous (B,C,H,W) fp32 batch" % fn
     B, C, H, W = clean.shape
     want = {"b": (B,), "bc": (B, C), "bcn": (B, C, W), "k": (len(plan.ksize), 21, 21), "bnn": (B, H, W), "c": (C,)}
     for (name, dt, shp), t in zip(_DEG_TABLES, tabs):
         assert t is None or (t.dtype == dt and tuple(t.shape) == want[shp] and t.is_contiguous() and t.device == clean.device), \
-            "degrade_batch: plan.%s must be a contiguous %s tensor of shape %s on %s" % (name, dt, want[shp], clean.device)
+            "%s: plan.%s must be a contiguous %s tensor of shape %s on %s" % (fn, name, dt, want[shp], clean.device)
     for t in dr:
         assert t is None or (t.dtype == torch.float32 and t.shape == clean.shape and t.is_contiguous() and t.device == clean.device), \
-            "degrade_batch: explicit draws are contiguous fp32 cubes of the batch's shape"
+            "%s: explicit draws are contiguous fp32 cubes of the batch's shape" % fn
     if od is not None:
-        assert od.dtype == torch.int64 and od.numel() == 1 and od.device == clean.device, "degrade_batch: a device ordinal is one int64"
+        assert od.dtype == torch.int64 and od.numel() == 1 and od.device == clean.device, "%s: a device ordinal is one int64" % fn
     if out is None:
-        out = (torch.empty_like(clean), torch.empty_like(clean))
+        out = (torch.empty_like(clean), torch.empty_like(clean) if want_clean else None)
     for t in out:
-        assert t.shape == clean.shape and t.dtype == torch.float32 and t.is_contiguous() and t.device == clean.device
-    assert out[0].data_ptr() != out[1].data_ptr() and clean.data_ptr() not in (out[0].data_ptr(), out[1].data_ptr()), "degrade_batch: distinct cubes"
+        assert t is None or (t.shape == clean.shape and t.dtype == torch.float32 and t.is_contiguous() and t.device == clean.device)
+    ptrs = [clean.data_ptr()] + [t.data_ptr() for t in out if t is not None]
+    assert out[0] is not None and len(set(ptrs)) == len(ptrs), "%s: distinct cubes" % fn
     host = [(ctypes.c_int32 * max(len(v), 1))(*v) for v in (plan.menu, plan.ksize, plan.sr_factor)]
     a = _lib.DegradeArgs(clean=_p(clean), degraded=_p(out[0]), clean_aug=_p(out[1]), menu=ctypes.addressof(host[0]),
                          ksize=ctypes.addressof(host[1]) if plan.ksize else None, sr_factor=ctypes.addressof(host[2]) if plan.sr_factor else None,
                          z=_p(dr[0]), u0=_p(dr[1]), u1=_p(dr[2]), ordinal_dev=_p(od), seed=ctypes.c_int64(int(seed) & 0xFFFFFFFFFFFFFFFF).value,
                          ordinal=0 if od is not None else int(ordinal), B=B, C=C, H=H, W=W, T=len(plan.menu), K=len(plan.ksize),
                          F=len(plan.sr_factor), **{n: _p(t) for (n, _, _), t in zip(_DEG_TABLES, tabs)})
-    _lib.check(lib.mphsir_degrade_batch(ctypes.byref(a), _stream(clean)), "degrade_batch")
-    _acct("degrade", 0.0, 12.0 * clean.numel())
+    _lib.check(getattr(lib, "mphsir_" + fn)(ctypes.byref(a), _stream(clean)), fn)
+    _acct("degrade", 0.0, (12.0 if out[1] is not None else 8.0) * clean.numel())
     return out
+
+
+def degrade_batch(clean, plan, *, seed, ordinal, draws=None, out=None):
+    """clean (B,C,N,N) fp32, plan: a DegradePlan -> (degraded, clean_aug), each sample degraded by the kind of its task and both cubes under
+    its flip / rotation plan.aug (degrade.augment's modes), in ONE launch on the current stream.  draws = (z, u0, u1), three (B,C,N,N)
+    fp32 cubes read at the un-augmented element, or None: Philox4x32-10 draws from (seed, ordinal, element).  ordinal: an int, or a
+    one-element int64 tensor on the device that the launch itself reads (a captured launch replays with whatever it holds then).
+    out = (degraded, clean_aug) to write into."""
+    assert out is None or (len(out) == 2 and out[1] is not None), "degrade_batch: out = (degraded, clean_aug)"
+    return _degrade("degrade_batch", clean, plan, seed, ordinal, draws, out)
+
+
+def degrade_planes(clean, plan, *, seed, ordinal, draws=None, out=None, want_clean=True):
+    """degrade_batch for planes of any size (mphsir_degrade_planes: 64 x 64 tiles with a halo, one launch): clean (B,C,H,W) fp32, the
+    plan's column tables (B,C,W), its cirrus (B,H,W); plan.aug may be None (mode 0 for every sample) and must be None when H != W.
+    -> (degraded, clean_aug), or (degraded, None) with want_clean=False (or out = (degraded, None)): the copy is then not written at all.
+    Where degrade_batch accepts the cube too, the results are bitwise its results."""
+    assert out is None or len(out) == 2, "degrade_planes: out = (degraded, clean_aug or None)"
+    return _degrade("degrade_planes", clean, plan, seed, ordinal, draws, out, want_clean)
 
 
 def patch_sample(arena, levels, levels_host, records, index, C, P, out=None, workspace=None):

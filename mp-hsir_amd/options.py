@@ -8,6 +8,8 @@ unknown flags are tolerated so that importing this module under pytest/torchrun 
 Additions (not present in the reference, all optional): --model, --precision, --steps_per_epoch, --graph,
 --synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade, --scene_dir, --crop_jitter.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
 into ['0','1'] (options.py:36) and `--classifier type=bool` treats any non-empty string as True.
+--fused_degrade 1 works at every --patch_size: a patch of up to 128 x 128 is degraded by the plane form of the launch, a larger one (256
+out of a --scene_dir store, say) by its tiled form, with the same plan and the same element values.
 """
 import argparse
 
@@ -50,7 +52,8 @@ _FLAGS = [
     ("--resume", dict(type=int, default=0, help="1: --ckpt_path also restores the optimizer state and continues at the saved "
                       "epoch + 1 (a checkpoint written by this script); 0 (default) = the reference's warm start: weights only, epoch 0")),
     ("--fused_degrade", dict(type=int, default=0, help="1: degrade every training batch in one HIP launch from a plan built without host "
-                             "synchronisation (degrade.DegradationSynthesizer(fused=True); no poissonN); 0 (default): the tensor programs")),
+                             "synchronisation (degrade.DegradationSynthesizer(fused=True); no poissonN; any --patch_size: patches beyond "
+                             "128 x 128 go through the tiled form of the launch); 0 (default): the tensor programs")),
     ("--scene_dir", dict(type=str, default="", help="with --synthetic 0: a directory of .mat / .npy cubes; the scene pyramid is built once, kept in "
                          "HBM, and every batch is cut out of it on the device (scene_store.SceneStore); excludes --db_path")),
     ("--crop_jitter", dict(type=int, default=0, help="1 (with --scene_dir): move every patch origin by a uniform offset below its level's stride")),

@@ -27,7 +27,11 @@ report); the default, --quality torch, is the tensor-program path and prints wha
 too) restores every tile under 4 (flips, half turn) or 8 (all flips and rotations; square tiles only) transforms of the training
 augmentation and averages the results mapped back (scene.SceneRestorer(ensemble=...)); without --tile the cropped cube is then a
 one-tile scene of that restorer, which for ensemble 1 is bitwise the plain forward.  --save_restored 1 writes
-<output_path>/<mode label>/restored_<name>.npy (fp32, (C,H,W)) in either case.  The degradations are the GPU functions of degrade.py.
+<output_path>/<mode label>/restored_<name>.npy (fp32, (C,H,W)) in either case.  The degradations are the GPU functions of degrade.py;
+--fused_degrade 1 (an addition, default 0) degrades every cube of modes 0-10 in ONE HIP launch instead (degrade.SceneDegrader: the
+same element values, no cube-sized temporary, no library convolution, draws that depend on --seed and the cube's ordinal only -- other
+random streams than the tensor programs', so other scores within the noise; with or without --tile / --ensemble).  Mode 11 (Poisson
+noise) has no fused form and ends the run with a message; mode 12 degrades nothing and ignores the flag.
 --ckpt_path evaluates a Lightning checkpoint of the reference (`net.` key prefix).
 """
 import argparse
@@ -87,6 +91,8 @@ def build_parser():
                    "metrics.py; fused: PSNR / SSIM / SAM by the fused HIP kernel (adds a sam column)")
     p.add_argument("--ensemble", type=int, default=1, choices=[1, 4, 8], help="self-ensemble: the mean over 4 (flips and the half turn) or 8 (all "
                    "flips and rotations; needs square tiles) transformed restorations of every tile, mapped back; 1: off")
+    p.add_argument("--fused_degrade", type=int, default=0, help="1: degrade every cube of modes 0-10 in one HIP launch (degrade.SceneDegrader; no "
+                   "Poisson mode 11); 0 (default): the tensor programs of degrade.py")
     p.add_argument("--save_restored", type=int, default=0, help="1: write <output_path>/<mode label>/restored_<name>.npy (fp32, (C,H,W))")
     return p
 
@@ -223,6 +229,11 @@ def evaluate_quality(o, net, dev):
     cfg_bands = net.patch_embed.proj.weight.shape[1]
     gen = torch.Generator(device=dev).manual_seed(o.seed)
     d = D.Draws(dev, o.seed + 1)
+    fused_degrader = None
+    if o.fused_degrade and o.mode != 12:
+        if o.mode == 11:
+            raise SystemExit("--fused_degrade 1: mode 11 is Poisson noise, which has no fused form (run it with --fused_degrade 0)")
+        fused_degrader = D.SceneDegrader(o.model, dev, o.seed + 1)
     scenes = o.tile > 0 or o.ensemble > 1
     restorers = {}
     if o.tile > 0:
@@ -239,6 +250,8 @@ def evaluate_quality(o, net, dev):
             check_whole_scene(o, name, clean)
         if o.mode == 12:
             degraded, pid = real, 1
+        elif fused_degrader is not None:
+            degraded, pid = fused_degrader(clean, o.mode, o)
         else:
             degraded, pid = degrade_for_mode(o, clean, d, o.model)
         if scenes:
