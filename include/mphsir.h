@@ -320,7 +320,8 @@ int mphsir_gated_mlp_wgrad_fits(int32_t C, int32_t chunks_per_wg, int dtype);
 
 /* ---- backward of the window-attention side of a PGSSTB block --------------------------------------
  * mphsir_combine_bwd: backward of mphsir_gemm_tok epi 2 (y = R + keep*(SA*gate[win] + acc), net/MP_HSIR.py
- *   :715-718,:153): dOut = keep*dY (written only if keep != NULL), dSA = dOut*gate[win],
+ *   :715-718,:153): dOut = keep*dY (written only if keep != NULL), dSA = dOut*gate[win] (optional: NULL when
+ *   mphsir_win_attn_bwd forms the total d_sa itself),
  *   dgate[win][c] = sum over the window's 64 tokens of dOut*SA.  All cubes (B,H,W,C), image order.
  * mphsir_win_attn_bwd: backward of the attention core of mphsir_win_attn_fwd (Spatial_Attention.forward
  *   :193-218) for d_sa = dSA + dmu[win]/64 (dmu = gradient w.r.t. the window mean that feeds the gate).
@@ -345,9 +346,17 @@ typedef struct mphsir_win_attn_bwd_args {
     int32_t B, H, W, C, heads, shift;
     int32_t head_split;       /* tuning: 0 = auto; n = the heads of a window are dealt to n workgroups (n divides heads) -- small launches
                                  (the latent level: 128 windows for 256 CUs) otherwise leave most of the chip idle; results identical */
+    /* optional, all four or none (mphsir_win_attn_bwd_dsa_fits): the kernel forms the total d_sa itself, per window row
+       dSAt = dT3[pix] WsT^T (fp32 accumulators) + dOut[pix]*gate[win] + dmu[win]/64, rounded once; dSA is then not read (may be NULL) */
+    const void* dT3;          /* [M][3C] image order: gradient of the global spectral branch's qkv(sa) (mphsir_spectral_dqkv_bwd's dT) */
+    const void* WsT;          /* [C][3C]: the weight mphsir_gemm_tok would take for that 1x1 conv's data gradient */
+    const void* dOut;         /* [M][C] image order: mphsir_combine_bwd's dOut (dY itself without DropPath) */
+    const float* gate;        /* [B*nW][C] */
 } mphsir_win_attn_bwd_args;
 int mphsir_win_attn_bwd(const mphsir_win_attn_bwd_args* a, int dtype, void* stream);
 int mphsir_win_attn_bwd_fits(int32_t C, int32_t heads, int dtype);
+int mphsir_win_attn_bwd_dsa_fits(int32_t C, int32_t heads, int dtype);   /* 1: C in {64, 128, 256}, 16-bit dtypes */
+int mphsir_win_attn_bwd_head_split(int32_t B, int32_t H, int32_t W, int32_t heads);   /* the split head_split = 0 chooses (1 from 512 windows on) */
 int mphsir_ln_bwd_win(const void* X, const void* dXNw, const void* dRes, const float* ln_w, void* dX, float* part,
                       int32_t B, int32_t H, int32_t W, int32_t C, int32_t shift, const float* ln_b, void* XN, int32_t linear,
                       int dtype, void* stream);

@@ -110,7 +110,8 @@ class MlpWgradArgs(_Args):
 class WinAttnBwdArgs(_Args):
     """mirror of struct mphsir_win_attn_bwd_args"""
     _fields_ = _SZ + [(n, c_void_p) for n in ("X", "dSA", "dmu", "ln_w", "ln_b", "Wqkv", "bqkv", "rpb", "WprojT", "dQKV", "XNw",
-                                         "dSAt", "drpb")] + [(n, c_int32) for n in ("B", "H", "W", "C", "heads", "shift", "head_split")]
+                                         "dSAt", "drpb")] + [(n, c_int32) for n in ("B", "H", "W", "C", "heads", "shift", "head_split")] + \
+               [(n, c_void_p) for n in ("dT3", "WsT", "dOut", "gate")]
 
 
 class FoldBwdArgs(_Args):
@@ -243,6 +244,8 @@ _SYMBOLS = {
     "mphsir_combine_bwd": (c_int, [c_void_p] * 7 + [c_int32] * 5 + [c_int, c_void_p]),
     "mphsir_win_attn_bwd": (c_int, [ctypes.POINTER(WinAttnBwdArgs), c_int, c_void_p]),
     "mphsir_win_attn_bwd_fits": (c_int, [c_int32, c_int32, c_int]),
+    "mphsir_win_attn_bwd_dsa_fits": (c_int, [c_int32, c_int32, c_int]),
+    "mphsir_win_attn_bwd_head_split": (c_int, [c_int32] * 4),
     "mphsir_ln_bwd_win": (c_int, [c_void_p] * 6 + [c_int32] * 5 + [c_void_p, c_void_p, c_int32, c_int, c_void_p]),
     "mphsir_ln_bwd_win_dxn": (c_int, [c_void_p] * 8 + [c_int32] * 5 + [c_int, c_void_p]),
     "mphsir_ln_bwd_win_dxn_fits": (c_int, [c_int32, c_int]),

@@ -273,7 +273,10 @@ def _pgsstb_attn_backward(blk, k1, saved, dy, extra=None):
     with ops.reduce_scope(leaf=True):      # every split partial of this backward is summed by ONE launch when the scope exits
         # (1) branch sum  y = x + keep*(sa*gate + out)
         f32_factors = dt == torch.float16 or mu.shape[0] <= 512
-        d_out, d_sa, dgate = ops.combine_bwd(dy, sa, gate, k1, shift)
+        # win_attn_bwd forms the total d_sa itself where it can and it pays: combine_bwd then leaves d_out * gate unwritten and the data gradient of
+        # the spectral 1x1 qkv conv (a K = 3C token GEMM onto d_sa) is not launched
+        own_dsa = ops.win_attn_bwd_dsa_fits(Cc, heads, dt) and ops.win_attn_bwd_dsa_pays(B, H, W, heads)
+        d_out, d_sa, dgate = ops.combine_bwd(dy, sa, gate, k1, shift, want_dsa=not own_dsa)
         # (3, issued first on a side branch) local spectral-prompt gate: one launch per block + one token-reduction GEMM
         # over the windows.  Factor rows in the compute dtype ride in the grouped 16-bit GEMM launch; fp16's narrow exponent
         # would flush the gate's tiny d-logits (w ~ 1/128 of an already small gradient), so that path keeps them in fp32
@@ -286,13 +289,17 @@ def _pgsstb_attn_backward(blk, k1, saved, dy, extra=None):
         dt3, d_sdw, dtemp, dwo = channel_attention_bwd_self(
             d_out.reshape(M, Cc), saved.t.reshape(B, H, W, 3 * Cc), sp["w9"], saved.v, saved.gp, saved.spart, saved.MbT,
             blk.gobal_spectral_attn.temperature, blk.gobal_spectral_attn.project_out.weight, heads, qk=saved.qk)
-        d_sa = ops.gemm_tok(dt3, sp["wqkvT"], epi=1, res=d_sa.reshape(M, Cc))    # + dt Wqkv  (1x1 conv backward)
+        if own_dsa:
+            branch = dict(dt3=dt3, wsT=sp["wqkvT"], d_out=d_out.reshape(M, Cc), gate=gate)
+        else:
+            branch = None
+            d_sa = ops.gemm_tok(dt3, sp["wqkvT"], epi=1, res=d_sa.reshape(M, Cc)).reshape(B, H, W, Cc)    # + dt Wqkv  (1x1 conv backward)
         d_sqkv = ops.gemm_tn(dt3, sa.reshape(M, Cc)).reshape(3 * Cc, Cc, 1, 1)
         dpg = tuple(gpg[k].reshape(getattr_path(blk.local_spectral_attn, k).shape) for k in _PG_KEYS)
         br.join()
         # (4) window attention core
-        dqkv, xnw, dsat, drpb = ops.win_attn_bwd(x, d_sa.reshape(B, H, W, Cc), dmu, pk["ln1"][0], pk["ln1"][1], pk["wqkv"], pk["bqkv"],
-                                                 pk["rpb"], pk["wprojT"], heads, shift)
+        dqkv, xnw, dsat, drpb = ops.win_attn_bwd(x, d_sa, dmu, pk["ln1"][0], pk["ln1"][1], pk["wqkv"], pk["bqkv"],
+                                                 pk["rpb"], pk["wprojT"], heads, shift, branch=branch)
         d_qkv_w, d_qkv_b = ops.gemm_tn(dqkv, xnw, colsum=True)
         dsat2 = dsat.reshape(M, Cc)
         d_proj_w, d_proj_b = ops.gemm_tn(dsat2, oattn.reshape(M, Cc), colsum=True)

@@ -8,6 +8,9 @@
 //                 Writes d[q|k|v] (window-token order), LN(x) (same order) and the total d_sa (image order),
 //                 so that every parameter gradient is a plain token-reduction GEMM / column sum done by
 //                 the caller, plus per-window partials of the relative-position-bias gradient.
+//                 Given dT3 / WsT / dOut / gate it forms the total d_sa itself: the data gradient of the global spectral
+//                 branch's 1x1 qkv conv (dT3 WsT^T, fp32 on the matrix cores) + d_out*gate[win] + dmu/64, rounded once --
+//                 the branch-sum part of d_sa and the K = 3C token GEMM that added onto it never reach HBM.
 //   ln_bwd_win    d_x = d_res + LayerNorm_backward(d_xn) with d_xn in window-token order (un-shift /
 //                 un-window by address arithmetic), plus per-window partials of d(norm1 weight/bias).
 // All reductions are ordered (no atomics): results are bitwise reproducible.
@@ -31,7 +34,7 @@ __device__ __forceinline__ long win_pixel(const WinGeom& g, int blk, int t) {
 struct CombBwdDev {
     const void* dY; const void* SA; const float* gate; const float* keep;
     void* dOut;      // optional: keep*dy (written only when keep != NULL)
-    void* dSA;       // d_out * gate[win]
+    void* dSA;       // optional: d_out * gate[win] (not needed when win_attn_bwd forms the total d_sa itself)
     float* dgate;    // [B*nW][C]
     WinGeom g; int C;
 };
@@ -68,7 +71,7 @@ __global__ __launch_bounds__(256) void combine_bwd_kernel(CombBwdDev a) {
                 acc[e] += d * sa.get(e);
             }
             if (a.keep && dOut) store16<T>(dOut + p, o);
-            store16<T>(dSA + p, s);
+            if (dSA) store16<T>(dSA + p, s);
         }
         for (int e = 0; e < VEC; ++e) red[grp * C + c0 + e] = acc[e];
     }
@@ -93,6 +96,26 @@ struct WinBwdDev {
     WinGeom g;
     int hsplit;                         // the heads of a window are dealt to hsplit workgroups (grid.y): small launches (the latent level has
                                         // 128 windows for 256 CUs) get one workgroup per (window, head group) instead of half a chip idle
+    // optional (all four or none; 16-bit, WinBwdDsa widths): the kernel forms the total d_sa itself and dSA is not read
+    const void* dT3;                    // [M][3C]  image order: gradient of the global spectral branch's qkv(sa)
+    const void* WsT;                    // [C][3C]  WsT[c][k] = spectral qkv.weight[k][c] (the weight gemm_tok takes for that data gradient)
+    const void* dOut;                   // [M][C]   image order: keep * dy
+    const float* gate;                  // [B*nW][C]
+};
+
+// The d_sa prologue, phase (a) of ln_bwd_win_dxn_kernel (ln_bwd_dxn.hip) run on gathered rows: a wave = 16 window rows x all C outputs,
+// its dT3 fragments straight from HBM / L2 (16 bytes per lane and K chunk, rows gathered through win_pixel), the rows of WsT through LDS in
+// groups of KGC K chunks with the next group requested before this group's barrier.  The stage lies at the start of the kernel's LDS,
+// where every tile is still unused; the C/16 accumulators die before phase (a).  Natural widths (the remote-sensing ones keep the
+// gemm_tok launch: 24 accumulator tiles at C = 384).
+template <class T, int C> struct WinBwdDsa {
+    static constexpr bool OK = sizeof(T) == 2 && (C == 64 || C == 128 || C == 256);
+    static constexpr int NB = C / 16, K = 3 * C, NKC = K / 32;
+    static constexpr int KGC = C <= 128 ? 3 : 2;                      // K chunks (of 32) per weight stage; divides NKC at every covered width
+    static constexpr int NGRP = NKC / KGC;
+    static constexpr int LDW = 32 * KGC + LDS_PAD_BYTES / (int)sizeof(T);
+    static constexpr int NWV = (C * KGC * 4 + 255) / 256;             // 16-byte weight vectors per thread and stage
+    static constexpr size_t BYTES = (size_t)C * LDW * sizeof(T);
 };
 
 // LDS plan.  Per head the kernel holds four row-major [64 tok][HDP] tiles (q, k, v, dO_h) and the two 64x64 matrices
@@ -157,7 +180,70 @@ __global__ __launch_bounds__(256, XR ? 3 : 1) void win_attn_bwd_kernel(WinBwdDev
     const T* Xg = reinterpret_cast<const T*>(a.XNw) + row0 * C;      // this window's rows of the two side outputs,
     const T* Dg = reinterpret_cast<const T*>(a.dSAt) + row0 * C;     // read back as MFMA operands after the barrier
 
-    // ---- LN(x) and the total d_sa: both side outputs (window-token order); LN(x) also into LDS when XL ----------
+    // ---- total d_sa = dT3 WsT^T + d_out * gate[win] + dmu / 64 (see WinBwdDsa), rounded once into the dSAt rows ----------
+    bool own_dsa = false;
+    if constexpr (WinBwdDsa<T, C>::OK) {
+        typedef WinBwdDsa<T, C> DG;
+        static_assert(DG::BYTES <= CF::BYTES && DG::NKC % DG::KGC == 0, "the weight stage lies inside the kernel's LDS plan");
+        own_dsa = a.dT3 != nullptr;
+        if (own_dsa) {
+            T* Ws = reinterpret_cast<T*>(smem_v);                                // [C][LDW]  rows of WsT, one K group
+            const T* WsT = reinterpret_cast<const T*>(a.WsT);
+            const int tok = wv * 16 + (lane & 15);
+            const long pix = win_pixel(a.g, blockIdx.x, tok);
+            const T* drow = reinterpret_cast<const T*>(a.dT3) + pix * DG::K + 8 * (lane >> 4);
+            Vec16<T> wreg[DG::NWV];
+            auto gload = [&](int g) __attribute__((always_inline)) {
+#pragma unroll
+                for (int i = 0; i < DG::NWV; ++i) {
+                    const int idx = tid + 256 * i;
+                    if (idx < C * DG::KGC * 4)
+                        wreg[i] = load16<T>(WsT + (long)(idx / (DG::KGC * 4)) * DG::K + g * 32 * DG::KGC + (idx % (DG::KGC * 4)) * VEC);
+                }
+            };
+            auto gstore = [&]() __attribute__((always_inline)) {
+#pragma unroll
+                for (int i = 0; i < DG::NWV; ++i) {
+                    const int idx = tid + 256 * i;
+                    if (idx < C * DG::KGC * 4) store16<T>(Ws + (idx / (DG::KGC * 4)) * DG::LDW + (idx % (DG::KGC * 4)) * VEC, wreg[i]);
+                }
+            };
+            f32x4 acc[DG::NB];
+#pragma unroll
+            for (int nb = 0; nb < DG::NB; ++nb) acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+            gload(0);
+#pragma unroll 1
+            for (int g = 0; g < DG::NGRP; ++g) {
+                frag_t df[DG::KGC];
+#pragma unroll
+                for (int kc = 0; kc < DG::KGC; ++kc) df[kc] = *reinterpret_cast<const frag_t*>(drow + (g * DG::KGC + kc) * 32);
+                if (g > 0) __syncthreads();                    // the previous group's fragments have been read
+                gstore();
+                __syncthreads();
+                if (g + 1 < DG::NGRP) gload(g + 1);
+#pragma unroll
+                for (int kc = 0; kc < DG::KGC; ++kc)
+#pragma unroll
+                    for (int nb = 0; nb < DG::NB; ++nb) mma(acc[nb], load_frag<T>(Ws, DG::LDW, nb * 16, kc * 32), df[kc]);
+            }
+            // transposed accumulators: lane = 4 consecutive channels of window row `tok`
+            const int cr = (lane >> 4) * 4;
+            const T* orow = reinterpret_cast<const T*>(a.dOut) + pix * C + cr;
+            const float* grow = a.gate + (long)blockIdx.x * C + cr;
+            const float* mrow = a.dmu + (long)blockIdx.x * C + cr;
+            T* dst = reinterpret_cast<T*>(a.dSAt) + (row0 + tok) * C + cr;
+#pragma unroll
+            for (int nb = 0; nb < DG::NB; ++nb) {
+                const f32x4 o = load4<T>(orow + nb * 16);
+                const f32x4 gt = *reinterpret_cast<const f32x4*>(grow + nb * 16), mu = *reinterpret_cast<const f32x4*>(mrow + nb * 16);
+                f32x4 tot;
+                for (int r = 0; r < 4; ++r) tot[r] = acc[nb][r] + o[r] * gt[r] + mu[r] * (1.0f / 64.0f);
+                store4<T>(dst + nb * 16, tot);
+            }
+            __syncthreads();                                   // the weight stage is read: the LN(x) tile may take its place
+        }
+    }
+    // ---- LN(x) and (unless formed above) the total d_sa: both side outputs (window-token order); LN(x) also into LDS when XL
     {
         constexpr int NV = C / VEC, VPT = NV / 4;
         const int t = tid >> 2, q = tid & 3;
@@ -191,9 +277,11 @@ __global__ __launch_bounds__(256, XR ? 3 : 1) void win_attn_bwd_kernel(WinBwdDev
             if (XL) store16<T>(Xs + t * CF::LDX + c0, o);
             if (XR) store16<T>(Qr + t * CF::LDX + c0, o);      // transit through the q|k tiles (written only from phase (a) on)
             store16<T>(xnw + c0, o);
-            Vec16<T> d = load16<T>(dSA + pix * C + c0);
-            for (int e = 0; e < VEC; ++e) d.set(e, d.get(e) + dmu[c0 + e] * (1.0f / 64.0f));
-            store16<T>(dst + c0, d);
+            if (!own_dsa) {
+                Vec16<T> d = load16<T>(dSA + pix * C + c0);
+                for (int e = 0; e < VEC; ++e) d.set(e, d.get(e) + dmu[c0 + e] * (1.0f / 64.0f));
+                store16<T>(dst + c0, d);
+            }
         }
         if (tid < 64) {
             const int nwx = a.g.W >> 3, nW = (a.g.H >> 3) * nwx, wi = blockIdx.x % nW;
@@ -625,10 +713,10 @@ extern "C" int mphsir_combine_bwd(const void* dY, const void* SA, const float* g
                                   float* dgate, int32_t B, int32_t H, int32_t W, int32_t C, int32_t shift, int dtype, void* stream) {
     using namespace mphsir;
     clear_error();
-    MPHSIR_REQUIRE(dY && SA && gate && dSA && dgate, "combine_bwd: null pointer");
+    MPHSIR_REQUIRE(dY && SA && gate && dgate, "combine_bwd: null pointer");
     MPHSIR_REQUIRE(MPHSIR_DTYPE_OK(dtype), "combine_bwd: dtype %d unsupported", dtype);
     MPHSIR_REQUIRE(geom_ok(B, H, W, shift) && C > 0 && C % 8 == 0, "combine_bwd: bad geometry");
-    MPHSIR_REQUIRE(aligned16(dY) && aligned16(SA) && aligned16(dSA) && (!dOut || aligned16(dOut)), "combine_bwd: 16-byte alignment required");
+    MPHSIR_REQUIRE(aligned16(dY) && aligned16(SA) && (!dSA || aligned16(dSA)) && (!dOut || aligned16(dOut)), "combine_bwd: 16-byte alignment required");
     CombBwdDev d{dY, SA, gate, keep, dOut, dSA, dgate, WinGeom{B, H, W, shift}, C};
     const int nblk = B * (H / 8) * (W / 8);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -641,25 +729,40 @@ extern "C" int mphsir_combine_bwd(const void* dY, const void* SA, const float* g
     return MPHSIR_OK;
 }
 
+extern "C" int mphsir_win_attn_bwd_head_split(int32_t B, int32_t H, int32_t W, int32_t heads) {
+    // the head split mphsir_win_attn_bwd chooses by itself (head_split = 0): double it until about 512 workgroups exist
+    if (B <= 0 || H < 8 || W < 8 || heads <= 0) return 1;
+    int hsplit = 1;
+    const long nwin = (long)B * (H / 8) * (W / 8);
+    while (nwin * hsplit < 512 && heads % (2 * hsplit) == 0) hsplit *= 2;
+    return hsplit;
+}
+
 extern "C" int mphsir_win_attn_bwd(const mphsir_win_attn_bwd_args* a, int dtype, void* stream) {
     using namespace mphsir;
     clear_error();
     MPHSIR_CHECK_ARGS(a, "win_attn_bwd");
-    MPHSIR_REQUIRE(a && a->X && a->dSA && a->dmu && a->ln_w && a->ln_b && a->Wqkv && a->bqkv && a->rpb && a->WprojT && a->dQKV &&
+    const bool own_dsa = a->dT3 || a->WsT || a->dOut || a->gate;      // the kernel forms the total d_sa itself: dSA is not read
+    MPHSIR_REQUIRE(a->X && (a->dSA || own_dsa) && a->dmu && a->ln_w && a->ln_b && a->Wqkv && a->bqkv && a->rpb && a->WprojT && a->dQKV &&
                        a->XNw && a->dSAt && a->drpb, "win_attn_bwd: null pointer");
     MPHSIR_REQUIRE(MPHSIR_DTYPE_OK(dtype), "win_attn_bwd: dtype %d unsupported", dtype);
     MPHSIR_REQUIRE(geom_ok(a->B, a->H, a->W, a->shift) && a->heads > 0 && a->C % a->heads == 0, "win_attn_bwd: bad geometry");
+    if (own_dsa) {
+        MPHSIR_REQUIRE(a->dT3 && a->WsT && a->dOut && a->gate, "win_attn_bwd: dT3, WsT, dOut and gate go together (all four or none)");
+        MPHSIR_REQUIRE(mphsir_win_attn_bwd_dsa_fits(a->C, a->heads, dtype),
+                       "win_attn_bwd: (C=%d, heads=%d, dtype=%d) does not form d_sa itself (ask mphsir_win_attn_bwd_dsa_fits)", a->C, a->heads, dtype);
+        MPHSIR_REQUIRE(aligned16(a->dT3) && aligned16(a->WsT) && aligned16(a->dOut) && aligned16(a->gate) && aligned16(a->dmu) && aligned16(a->dSAt),
+                       "win_attn_bwd: 16-byte alignment required");
+    }
     // fewer than two workgroups per CU: deal the heads of a window to 2, 4, .. workgroups (measured, tools/bench_winb_hs.py: 128 windows
     // of C = 256 / 8 heads 92.9 -> 36.7 us with 4 groups, 42.7 with 8; 256 windows 98 -> 63 with 2; 512 windows are best left whole)
-    int hsplit = 1;
-    const long nwin = (long)a->B * (a->H / 8) * (a->W / 8);
-    while (nwin * hsplit < 512 && a->heads % (2 * hsplit) == 0) hsplit *= 2;
+    int hsplit = mphsir_win_attn_bwd_head_split(a->B, a->H, a->W, a->heads);
     if (a->head_split > 0) {
         MPHSIR_REQUIRE(a->heads % a->head_split == 0, "win_attn_bwd: head_split=%d must divide heads=%d", a->head_split, a->heads);
         hsplit = a->head_split;
     }
     WinBwdDev d{a->X, a->dSA, a->dmu, a->ln_w, a->ln_b, a->Wqkv, a->bqkv, a->rpb, a->WprojT, a->dQKV, a->XNw, a->dSAt, a->drpb,
-                WinGeom{a->B, a->H, a->W, a->shift}, hsplit};
+                WinGeom{a->B, a->H, a->W, a->shift}, hsplit, a->dT3, a->WsT, a->dOut, a->gate};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     return MPHSIR_DISPATCH_T(dtype, (dispatch_win_bwd<T_>(d, a->C, a->C / a->heads, s)));
 }
@@ -672,6 +775,11 @@ extern "C" int mphsir_win_attn_bwd_fits(int32_t C, int32_t heads, int dtype) {
     MPHSIR_WINB_SHAPES(MPHSIR_WINB_CASE)
 #undef MPHSIR_WINB_CASE
     return 0;
+}
+
+extern "C" int mphsir_win_attn_bwd_dsa_fits(int32_t C, int32_t heads, int dtype) {
+    // the widths of WinBwdDsa (the natural-scene net's), 16-bit types, among the instantiated (width, head_dim)
+    return ((dtype == MPHSIR_BF16 || dtype == MPHSIR_F16) && (C == 64 || C == 128 || C == 256) && mphsir_win_attn_bwd_fits(C, heads, dtype)) ? 1 : 0;
 }
 
 extern "C" int mphsir_ln_bwd_win(const void* X, const void* dXNw, const void* dRes, const float* ln_w, void* dX, float* part,

@@ -1574,18 +1574,20 @@ def gated_mlp_wgrad(xn, dm, W1, b1, W2T, hid, nch=None, ranges=None):
     return dW1, db1[0], dW2, db2
 
 
-def combine_bwd(dy, sa, gate, keep, shift):
-    """dy, sa (B,H,W,C) -> (d_out (= dy when keep is None), d_sa, dgate (B*nW,C) fp32)."""
+def combine_bwd(dy, sa, gate, keep, shift, want_dsa=True):
+    """dy, sa (B,H,W,C) -> (d_out (= dy when keep is None), d_sa, dgate (B*nW,C) fp32).
+    want_dsa=False: d_sa = d_out * gate is not written and None is returned in its place (win_attn_bwd branch=... forms the total d_sa)."""
     lib = _lib.load()
     _check(dy, sa, gate, keep)
     B, H, W, C = dy.shape
     assert dy.is_contiguous() and sa.is_contiguous()
     d_out = torch.empty_like(dy) if keep is not None else dy
-    d_sa = torch.empty_like(dy)
+    d_sa = torch.empty_like(dy) if want_dsa else None
     dgate = torch.empty_like(gate)
     _lib.check(lib.mphsir_combine_bwd(_p(dy), _p(sa), _p(gate), _p(keep), _p(d_out) if keep is not None else None, _p(d_sa),
                                       _p(dgate), B, H, W, C, shift, _DT[dy.dtype], _stream(dy)), "combine_bwd")
-    _acct("combine_bwd", 4.0 * dy.numel(), 4.0 * dy.numel() * dy.element_size())
+    passes = 2.0 + (keep is not None) + bool(want_dsa)      # reads dy, sa; writes d_out (DropPath) and d_sa
+    _acct("combine_bwd", passes * dy.numel(), passes * dy.numel() * dy.element_size())
     return d_out, d_sa, dgate
 
 
@@ -1593,13 +1595,41 @@ def win_attn_bwd_fits(C, heads, dtype):
     return bool(_lib.load().mphsir_win_attn_bwd_fits(C, heads, _DT[dtype]))
 
 
-def win_attn_bwd(x, dsa, dmu, ln_w, ln_b, Wqkv, bqkv, rpb, WprojT, heads, shift, head_split=0):
-    """-> dqkv (M,3C) and xn (M,C) in window-token order, dsa_total (B,H,W,C), drpb (B*nW,225,heads) fp32."""
+BRANCH_BWD_FUSED = os.environ.get("MPHSIR_BRANCH_BWD_FUSED", "1") == "1"     # 0: the gemm_tok launch (and combine_bwd's d_sa) it replaces
+
+
+def win_attn_bwd_dsa_fits(C, heads, dtype):
+    """CAPABILITY: win_attn_bwd can form the total d_sa itself (branch=...) -- the natural widths in the 16-bit types, switch on."""
+    return BRANCH_BWD_FUSED and dtype in _HALF and bool(_lib.load().mphsir_win_attn_bwd_dsa_fits(C, heads, _DT[dtype]))
+
+
+# TUNING: where the host takes that path.  It pays where one workgroup owns a window.  Where the library deals the heads of a window to
+# several workgroups (mphsir_win_attn_bwd_head_split > 1: fewer than 512 windows), each of them repeats the whole K = 3C product behind
+# its own chain of weight stages, and the token GEMM it replaces is the cheaper launch (DESIGN.md section 5 has the measurements).
+BRANCH_BWD_SPLIT_HEADS_TOO = False       # True: also there (the whole-block tests run at 8 windows)
+
+
+def win_attn_bwd_dsa_pays(B, H, W, heads):
+    return BRANCH_BWD_SPLIT_HEADS_TOO or _lib.load().mphsir_win_attn_bwd_head_split(B, H, W, heads) == 1
+
+
+def win_attn_bwd(x, dsa, dmu, ln_w, ln_b, Wqkv, bqkv, rpb, WprojT, heads, shift, head_split=0, branch=None):
+    """-> dqkv (M,3C) and xn (M,C) in window-token order, dsa_total (B,H,W,C), drpb (B*nW,225,heads) fp32.
+    branch = dict(dt3 (M,3C), wsT (C,3C), d_out (M,C), gate (B*nW,C)) with dsa=None (win_attn_bwd_dsa_fits): the launch forms
+    dsa_total = dt3 wsT^T + d_out*gate[win] + dmu/64 itself, rounded once."""
     lib = _lib.load()
     _check(x, dsa, dmu, Wqkv, WprojT)
     B, H, W, C = x.shape
     M = B * H * W
-    assert x.is_contiguous() and dsa.is_contiguous() and WprojT.shape == (C, C)
+    assert x.is_contiguous() and WprojT.shape == (C, C)
+    if branch is None:
+        assert dsa.is_contiguous()
+    else:
+        dt3, wsT, d_out, gate = branch["dt3"], branch["wsT"], branch["d_out"], branch["gate"]
+        _check(x, dt3, wsT, d_out, gate)
+        assert dsa is None and dt3.is_contiguous() and d_out.is_contiguous() and wsT.is_contiguous() and gate.is_contiguous()
+        assert dt3.shape == (M, 3 * C) and wsT.shape == (C, 3 * C) and d_out.numel() == M * C and gate.shape == (M // 64, C)
+        assert dt3.dtype == wsT.dtype == d_out.dtype == x.dtype and gate.dtype == dmu.dtype == torch.float32
     dqkv = torch.empty((M, 3 * C), dtype=x.dtype, device=x.device)
     xnw = torch.empty((M, C), dtype=x.dtype, device=x.device)
     dsat = torch.empty_like(x)
@@ -1609,8 +1639,11 @@ def win_attn_bwd(x, dsa, dmu, ln_w, ln_b, Wqkv, bqkv, rpb, WprojT, heads, shift,
     a.Wqkv, a.bqkv, a.rpb, a.WprojT = _p(Wqkv), _p(bqkv), _p(rpb), _p(WprojT)
     a.dQKV, a.XNw, a.dSAt, a.drpb = _p(dqkv), _p(xnw), _p(dsat), _p(drpb)
     a.B, a.H, a.W, a.C, a.heads, a.shift, a.head_split = B, H, W, C, heads, shift, head_split
+    if branch is not None:
+        a.dT3, a.WsT, a.dOut, a.gate = _p(dt3), _p(wsT), _p(d_out), _p(gate)
     _lib.check(lib.mphsir_win_attn_bwd(ctypes.byref(a), _DT[x.dtype], _stream(x)), "win_attn_bwd")
-    _acct("win_attn_bwd", M * (8.0 * C * C + 10.0 * 64 * C), 7.0 * M * C * x.element_size())
+    # with the d_sa prologue: + the K = 3C GEMM (6 C^2 per token) and the dt3 rows (3C per token) in place of nothing
+    _acct("win_attn_bwd", M * ((8.0 if branch is None else 14.0) * C * C + 10.0 * 64 * C), (7.0 if branch is None else 10.0) * M * C * x.element_size())
     return dqkv, xnw, dsat, drpb
 
 
