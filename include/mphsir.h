@@ -814,6 +814,60 @@ int mphsir_flat_adamw_scaled(float* p, const float* g, float* m, float* v, int64
                              float weight_decay, float grad_scale, const float* hyper, const float* scaler, void* stream);
 int mphsir_scaler_update(float* scaler, float growth_factor, float backoff_factor, int32_t growth_interval, void* stream);
 
+/* ---- global-norm gradient clipping and EMA weights on the arenas (off unless the caller asks: mp-hsir_amd/engine.py) ------------
+ * stats: device fp32[4] = [0] the gradient norm of the last call, [1] the clip factor coef of the last call, [2] steps skipped so
+ *   far because their norm was not finite, [3] "skip this step" flag, 0 or 1, rewritten by every mphsir_grad_norm call.
+ * mphsir_grad_norm: S = sum g[i]^2 over the n (n % 4 == 0, padding zero-filled) gradients, every square and every partial sum in
+ *   float64 (the square of an fp32 value is exact there: 1e30 and 1e-30 neither overflow nor vanish).  Launch 1 writes one float64
+ *   partial per workgroup to `workspace` (mphsir_grad_norm_workspace_bytes(n) bytes, 8-byte aligned), launch 2 (one workgroup)
+ *   combines them in a fixed order: no atomics, bitwise equal from run to run, nothing read back by the host, capturable.
+ *     norm = sqrt(S) * grad_scale / (scaler ? scaler[0] : 1)        (scaler: the loss-scaler state above, optional)
+ *     coef = min(1, max_norm / (norm + 1e-6)) in float64, rounded once to fp32       (torch.nn.utils.clip_grad_norm_'s rule)
+ *   stats[0] = (float)norm, stats[1] = coef, stats[3] = 0.  A norm that is not finite (an inf or a NaN among the gradients) gives
+ *   coef = 0, stats[3] = 1 and stats[2] += 1.  max_norm > 0; +inf is legal and means "measure only": coef is exactly 1 then.
+ * mphsir_flat_adamw_ex: mphsir_flat_adamw / mphsir_flat_adamw_scaled in one launch and one pass with two optional additions:
+ *   stats (nullable): the gradient enters as ge = (g * grad_scale_effective) * stats[1]; the whole update is skipped when stats[3] != 0;
+ *   ema (nullable, n fp32, 16-byte aligned): ema += (1 - d) * (p_new - ema) with the parameter the step has just formed.
+ *   hyper (nullable device fp32) = [lr, 1-beta1^step, sqrt(1-beta2^step)] and, when ema is given, [3] = d; without hyper d = ema_decay
+ *   (0 <= d < 1) and lr / step are the host values (step 1-based).  scaler (nullable): as for mphsir_flat_adamw_scaled -- g is divided
+ *   by scaler[0], the step is skipped when scaler[2] != 0, the bias corrections use scaler[3] + 1.  A skipped step leaves p, m, v and
+ *   ema untouched.  The arithmetic on p / m / v keeps the order of mphsir_flat_adamw: with stats == NULL or stats[1] == 1, and
+ *   ema == NULL, the result is BITWISE that of mphsir_flat_adamw (with a scaler: of mphsir_flat_adamw_scaled).
+ * Both refuse (MPHSIR_EINVAL, nothing launched): another struct_size, a null or misaligned arena, n <= 0 or n % 4 != 0, a workspace
+ *   that is too small or not 8-byte aligned, max_norm <= 0 or NaN, ema_decay outside [0, 1), null stats in mphsir_grad_norm.
+ * (Declared as `struct ...; typedef ...;` because these are the first args structs with float members.)                          */
+struct mphsir_grad_norm_args {
+    uint32_t struct_size;       /* = sizeof(this struct), set by the caller: any other value is rejected with MPHSIR_EINVAL */
+    const float* g;
+    int64_t n;
+    float grad_scale;
+    float max_norm;
+    const float* scaler;
+    void* workspace;
+    int64_t workspace_bytes;
+    float* stats;
+};
+typedef struct mphsir_grad_norm_args mphsir_grad_norm_args;
+int64_t mphsir_grad_norm_workspace_bytes(int64_t n);
+int mphsir_grad_norm(const mphsir_grad_norm_args* a, void* stream);
+struct mphsir_flat_adamw_ex_args {
+    uint32_t struct_size;       /* = sizeof(this struct), set by the caller: any other value is rejected with MPHSIR_EINVAL */
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    float* ema;
+    int64_t n;
+    float lr, beta1, beta2, eps, weight_decay, grad_scale;
+    int32_t step;
+    float ema_decay;
+    const float* hyper;
+    const float* scaler;
+    const float* stats;
+};
+typedef struct mphsir_flat_adamw_ex_args mphsir_flat_adamw_ex_args;
+int mphsir_flat_adamw_ex(const mphsir_flat_adamw_ex_args* a, void* stream);
+
 /* ---- flat-arena utilities -------------------------------------------------------------------------
  * reduce_parts: dst[b][i] = sum_{s < nsplit} src[b*src_batch_stride + s*stride + i], i < n, b < nbatch, summed in a
  * fixed order (a function of nsplit and n only: deterministic), for up to MPHSIR_REDUCE_MAX_SEGS independent segments in ONE launch.  Replaces the

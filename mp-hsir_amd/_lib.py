@@ -176,6 +176,20 @@ class PatchSampleArgs(_Args):
                [("workspace_bytes", c_int64), ("arena_elems", c_int64)] + [(n, c_int32) for n in ("n_levels", "n_records", "B", "C", "P")]
 
 
+# The two optimizer structs hold float members; tests/test_optim_ex_meta.py compares them with include/mphsir.h field by field.
+class GradNormArgs(_Args):
+    """ctypes image of mphsir_grad_norm_args"""
+    _fields_ = _SZ + [("g", c_void_p), ("n", c_int64), ("grad_scale", ctypes.c_float), ("max_norm", ctypes.c_float), ("scaler", c_void_p),
+                      ("workspace", c_void_p), ("workspace_bytes", c_int64), ("stats", c_void_p)]
+
+
+class FlatAdamwExArgs(_Args):
+    """ctypes image of mphsir_flat_adamw_ex_args"""
+    _fields_ = _SZ + [(n, c_void_p) for n in ("p", "g", "m", "v", "ema")] + [("n", c_int64)] + \
+               [(n, ctypes.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "grad_scale")] + \
+               [("step", c_int32), ("ema_decay", ctypes.c_float)] + [(n, c_void_p) for n in ("hyper", "scaler", "stats")]
+
+
 class TnProblem(ctypes.Structure):
     """mirror of struct mphsir_gemm_tn_problem"""
     _fields_ = [("A", c_void_p), ("lda", c_int64), ("B", c_void_p), ("ldb", c_int64), ("Cpart", c_void_p), ("colsum_part", c_void_p),
@@ -241,6 +255,9 @@ _SYMBOLS = {
     "mphsir_flat_adamw_scaled": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                          ctypes.c_float, ctypes.c_float, ctypes.c_float, c_void_p, c_void_p, c_void_p]),
     "mphsir_scaler_update": (c_int, [c_void_p, ctypes.c_float, ctypes.c_float, c_int32, c_void_p]),
+    "mphsir_grad_norm_workspace_bytes": (c_int64, [c_int64]),
+    "mphsir_grad_norm": (c_int, [ctypes.POINTER(GradNormArgs), c_void_p]),
+    "mphsir_flat_adamw_ex": (c_int, [ctypes.POINTER(FlatAdamwExArgs), c_void_p]),
     "mphsir_combine_bwd": (c_int, [c_void_p] * 7 + [c_int32] * 5 + [c_int, c_void_p]),
     "mphsir_win_attn_bwd": (c_int, [ctypes.POINTER(WinAttnBwdArgs), c_int, c_void_p]),
     "mphsir_win_attn_bwd_fits": (c_int, [c_int32, c_int32, c_int]),

@@ -18,6 +18,7 @@ Re-expresses what the reference gets implicitly from pytorch-lightning (train.py
     SURVEY Q3) are detected on the first step and kept out of the arenas -- the reference's AdamW
     skips them too (grad is None), so no weight decay is applied to them.
 """
+import contextlib
 import os
 import torch
 import torch.distributed as dist
@@ -180,7 +181,7 @@ def _external_events_work(dev):
 class DataParallelEngine:
     def __init__(self, net, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, bucket_mb=32, process_group=None,
                  loss_fn=l1_after_clamp, use_graph=False, graph_warmup=2, use_pack_plan=True, loss_scaling="auto",
-                 init_scale=65536.0, growth_interval=2000):
+                 init_scale=65536.0, growth_interval=2000, grad_clip=None, ema_decay=None, ema_warmup=True):
         self.net, self.lr, self.betas, self.eps, self.wd = net, lr, betas, eps, weight_decay
         self.loss_fn = loss_fn
         self.pg = process_group
@@ -205,6 +206,15 @@ class DataParallelEngine:
         # "auto": on exactly when the network computes in float16.
         self.loss_scaling, self.init_scale, self.growth_interval = loss_scaling, init_scale, growth_interval
         self.scaler = None
+        # Optional, both off by default (then _optimizer_step issues exactly the launches it always did):
+        #   grad_clip  clip the global L2 norm of the (mean) gradient to this value, torch.nn.utils.clip_grad_norm_'s rule; a step whose
+        #              norm is not finite is skipped on the device.  Measured by ops.grad_norm, applied inside ops.flat_adamw_ex.
+        #   ema_decay  keep an exponential moving average of the arena parameters in flat_ema, updated by the same AdamW launch;
+        #              ema_warmup: decay d_t = min(ema_decay, (1 + t) / (10 + t)), t = the number of the step being taken (1-based).
+        assert grad_clip is None or grad_clip > 0, "grad_clip must be positive (None: off), got %r" % (grad_clip,)
+        assert ema_decay is None or 0.0 <= ema_decay < 1.0, "ema_decay must lie in [0, 1) (None: off), got %r" % (ema_decay,)
+        self.grad_clip, self.ema_decay, self.ema_warmup = grad_clip, ema_decay, ema_warmup
+        self.flat_ema = self.optim_stats = self._gn_ws = None
         if self.world > 1:      # DDP's initial parameter broadcast (rank 0 -> all), one flat message
             ps = [p for p in net.parameters()]
             flat = torch.cat([p.data.reshape(-1).float() for p in ps])
@@ -245,6 +255,12 @@ class DataParallelEngine:
         if count:
             self.buckets.append([start, total, count])
         self.arena = (used, offs, total)
+        if self.ema_decay is not None:
+            self.flat_ema = self.flat_p.clone()
+        if self.grad_clip is not None or self.ema_decay is not None:
+            self.optim_stats = ops.new_optim_stats(dev)
+        if self.grad_clip is not None:
+            self._gn_ws = ops.grad_norm_workspace(self.flat_g)
         # built here, outside any capture: its pinned tables cannot be allocated while a stream is capturing (a capture at the
         # very first hand-over -- graph_warmup=1 -- would otherwise be invalidated)
         self._multi_copy = ops.MultiCopy(self.flat_g.device, len(used)) if used else None
@@ -363,7 +379,23 @@ class DataParallelEngine:
     def _optimizer_step(self, lr, hyper=None):
         """AdamW over the arenas (1/world folded in); fp16 path: non-finite check + unscale + skip + scale update"""
         gs = 1.0 / self.world
-        if self.scaler is not None:
+        if self.grad_clip is not None or self.ema_decay is not None:
+            # grad_check (scaler) -> grad_norm (clip) -> flat_adamw_ex -> scaler_update (scaler): plain launches, captured with the step.
+            # grad_scale stays 1 / world: the norm is that of the mean gradient.  Without a scaler (bf16, fp32) a norm that is not finite
+            # skips the step ON THE DEVICE while step_count has already advanced on the host: Adam's bias corrections (and the EMA
+            # warm-up) are then one step ahead per skipped step -- negligible after warm-up, and nothing is read back to avoid it.
+            sc = self.scaler
+            if sc is not None:
+                ops.grad_check(self.flat_g, sc)
+            if self.grad_clip is not None:
+                ops.grad_norm(self.flat_g, self.optim_stats, self.grad_clip, gs, scaler=sc, workspace=self._gn_ws)
+            ops.flat_adamw_ex(self.flat_p, self.flat_g, self.flat_m, self.flat_v, 0.0 if hyper is not None else lr,
+                              0 if hyper is not None else self.step_count, self.betas[0], self.betas[1], self.eps, self.wd, gs, hyper=hyper,
+                              scaler=sc, stats=self.optim_stats if self.grad_clip is not None else None, ema=self.flat_ema,
+                              ema_decay=0.0 if hyper is not None or self.flat_ema is None else self._ema_decay_at(self.step_count))
+            if sc is not None:
+                ops.scaler_update(sc, interval=self.growth_interval)
+        elif self.scaler is not None:
             ops.scaled_adamw_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.scaler, 0.0 if hyper is not None else lr,
                                   self.betas[0], self.betas[1], self.eps, self.wd, gs, hyper=hyper, interval=self.growth_interval)
         elif hyper is not None:
@@ -375,7 +407,12 @@ class DataParallelEngine:
 
     def _hyper_values(self, lr, step):
         import math
-        return [lr, 1.0 - self.betas[0] ** step, math.sqrt(1.0 - self.betas[1] ** step)]
+        vals = [lr, 1.0 - self.betas[0] ** step, math.sqrt(1.0 - self.betas[1] ** step)]
+        return vals + [self._ema_decay_at(step)] if self.ema_decay is not None else vals
+
+    def _ema_decay_at(self, step):
+        """the EMA decay of optimizer step `step` (1-based), computed on the host and handed to the kernel"""
+        return min(self.ema_decay, (1.0 + step) / (10.0 + step)) if self.ema_warmup else self.ema_decay
 
     _HYPER_SLOTS = 4
 
@@ -415,7 +452,7 @@ class DataParallelEngine:
         if self._graph is None:
             self._graph_key = key
             self._sx, self._sc, self._sp = degraded.clone(), clean.clone(), prompt.clone()
-            self._hyper = torch.zeros(3, dtype=torch.float32, device=dev)
+            self._hyper = torch.zeros(4 if self.ema_decay is not None else 3, dtype=torch.float32, device=dev)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
@@ -485,8 +522,13 @@ class DataParallelEngine:
         used, offs, _ = self.arena
         m = {names[id(p)]: self.flat_m[o:o + p.numel()].view(p.shape).detach().cpu().clone() for p, o in zip(used, offs)}
         v = {names[id(p)]: self.flat_v[o:o + p.numel()].view(p.shape).detach().cpu().clone() for p, o in zip(used, offs)}
-        return {"step": self.step_count, "exp_avg": m, "exp_avg_sq": v,
-                "loss_scaler": None if self.scaler is None else self.scaler.detach().cpu().clone()}
+        state = {"step": self.step_count, "exp_avg": m, "exp_avg_sq": v,
+                 "loss_scaler": None if self.scaler is None else self.scaler.detach().cpu().clone()}
+        if self.flat_ema is not None:
+            state["ema"] = {names[id(p)]: self.flat_ema[o:o + p.numel()].view(p.shape).detach().cpu().clone() for p, o in zip(used, offs)}
+        if self.optim_stats is not None:
+            state["optim_stats"] = self.optim_stats.detach().cpu().clone()
+        return state
 
     def load_optimizer_state(self, state):
         """restore what optimizer_state() returned; call any time before or after the first step (it is applied as soon
@@ -517,6 +559,55 @@ class DataParallelEngine:
             if n in state["exp_avg"]:
                 self.flat_m[o:o + p.numel()].copy_(state["exp_avg"][n].reshape(-1))
                 self.flat_v[o:o + p.numel()].copy_(state["exp_avg_sq"][n].reshape(-1))
+        if self.flat_ema is not None:
+            self.flat_ema.copy_(self.flat_p)             # a state without "ema" (or without this parameter): the EMA starts from the loaded parameters
+            for p, o in zip(used, offs):
+                if names[id(p)] in state.get("ema", {}):
+                    self.flat_ema[o:o + p.numel()].copy_(state["ema"][names[id(p)]].reshape(-1))
+        if self.optim_stats is not None and state.get("optim_stats") is not None:
+            self.optim_stats.copy_(state["optim_stats"])
+
+    # ---- clip statistics and the averaged weights ------------------------------------------------------------------------
+    def grad_stats(self):
+        """{'norm', 'coef', 'skipped'} of the last optimizer step: the gradient norm before clipping, the factor applied, the steps
+        skipped so far for a norm that was not finite.  ONE device-to-host transfer: call it when logging, not every step."""
+        if self.optim_stats is None:
+            return {"norm": 0.0, "coef": 1.0, "skipped": 0}
+        s = self.optim_stats.detach().cpu().tolist()
+        return {"norm": s[0], "coef": s[1], "skipped": int(s[2])}
+
+    def ema_state_dict(self):
+        """the network's state_dict() with the EMA value in place of every arena parameter; buffers and parameters without a gradient
+        keep their live values"""
+        assert self.ema_decay is not None, "ema_state_dict: the engine was built without ema_decay"
+        sd = dict(self.net.state_dict())
+        if self.flat_ema is None:                       # before the first step: the EMA is the parameters
+            return sd
+        names = {id(p): n for n, p in self.net.named_parameters()}
+        used, offs, _ = self.arena
+        for p, o in zip(used, offs):
+            sd[names[id(p)]] = self.flat_ema[o:o + p.numel()].view(p.shape).detach().clone()
+        return sd
+
+    def _swap_ema(self):
+        tmp = self.flat_p.clone()
+        self.flat_p.copy_(self.flat_ema)
+        self.flat_ema.copy_(tmp)
+        ops.bump_weight_epoch()
+        if self.plan is not None:
+            self.plan.refresh()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """inside the block the network computes with the EMA weights: the CONTENTS of flat_p and flat_ema are swapped (the parameters
+        are views of flat_p and a captured step reads it by address, so nothing else has to change), the packed-weight caches follow
+        through the weight epoch and the pack plan; swapped back on exit.  Do not call train_step inside."""
+        assert self.flat_ema is not None, "ema_weights: needs ema_decay and at least one step taken"
+        self._swap_ema()
+        try:
+            yield self
+        finally:
+            self._swap_ema()
 
     def finish(self):
         """call before using the network eagerly again after graph-mode training (packed-weight caches were last

@@ -1347,6 +1347,72 @@ def scaled_adamw_step(p, g, m, v, scaler, lr, beta1=0.9, beta2=0.999, eps=1e-8, 
     bump_weight_epoch()
 
 
+def new_optim_stats(device):
+    """device state of mphsir_grad_norm (include/mphsir.h): fp32 [gradient norm, clip factor, steps skipped so far, skip flag of this
+    step]; the clip factor starts at 1."""
+    return torch.tensor([0.0, 1.0, 0.0, 0.0], dtype=torch.float32, device=device)
+
+
+def grad_norm_workspace(g):
+    """the float64 block partials mphsir_grad_norm needs for the arena g (caller-owned: a captured launch keeps its address)"""
+    nbytes = _lib.load().mphsir_grad_norm_workspace_bytes(g.numel())
+    if nbytes < 0:
+        raise RuntimeError("mp-hsir_amd: grad_norm refuses an arena of %d elements (a positive multiple of 4)" % g.numel())
+    return torch.empty((nbytes // 8,), dtype=torch.float64, device=g.device)
+
+
+def grad_norm(g, stats, max_norm=float("inf"), grad_scale=1.0, scaler=None, workspace=None):
+    """stats[0] = the L2 norm of g * grad_scale (/ scaler[0]) summed in float64, stats[1] = min(1, max_norm / (norm + 1e-6)); a norm
+    that is not finite sets the skip flag stats[3] and counts in stats[2] (include/mphsir.h).  Two launches on the current stream, no
+    atomics, nothing read back.  max_norm = inf: measure only.  workspace: grad_norm_workspace(g), allocated when not given."""
+    lib = _lib.load()
+    _check(g, stats, scaler, workspace)
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.dim() == 1, "grad_norm: a flat contiguous fp32 arena"
+    assert stats.dtype == torch.float32 and stats.numel() == 4 and stats.is_contiguous() and stats.device == g.device, "grad_norm: stats is fp32[4] on the arena's device"
+    assert scaler is None or (scaler.dtype == torch.float32 and scaler.numel() == 4 and scaler.device == g.device), "grad_norm: scaler is fp32[4]"
+    if workspace is None:
+        workspace = grad_norm_workspace(g)
+    assert workspace.dtype == torch.float64 and workspace.is_contiguous() and workspace.device == g.device, "grad_norm: a float64 workspace on the arena's device"
+    a = _lib.GradNormArgs(g=_p(g), n=g.numel(), grad_scale=grad_scale, max_norm=max_norm, scaler=_p(scaler), workspace=_p(workspace),
+                          workspace_bytes=8 * workspace.numel(), stats=_p(stats))
+    _lib.check(lib.mphsir_grad_norm(ctypes.byref(a), _stream(g)), "grad_norm")
+    _acct("grad_norm", 2.0 * g.numel(), 4.0 * g.numel())
+    return stats
+
+
+def flat_adamw_ex(p, g, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2, grad_scale=1.0, hyper=None, scaler=None,
+                  stats=None, ema=None, ema_decay=0.0):
+    """flat_adamw with the optional clip factor of grad_norm (stats) and an optional EMA arena updated in the same pass
+    (ema += (1 - d) (p_new - ema)); scaler: the fp16 path's state, as for scaled_adamw_step (grad_check and scaler_update stay the
+    caller's launches).  hyper: device fp32 [lr, 1-beta1^step, sqrt(1-beta2^step)] plus [3] = d when ema is given.  Without stats and
+    without ema the result is bitwise that of flat_adamw / mphsir_flat_adamw_scaled (include/mphsir.h)."""
+    lib = _lib.load()
+    _check(p, g, m, v, ema, hyper, scaler, stats)
+    assert p.dtype == torch.float32 and p.is_contiguous() and p.numel() == g.numel() == m.numel() == v.numel()
+    assert ema is None or (ema.dtype == torch.float32 and ema.is_contiguous() and ema.numel() == p.numel()), "flat_adamw_ex: ema is an fp32 arena of p's length"
+    assert hyper is None or (hyper.dtype == torch.float32 and hyper.numel() >= (4 if ema is not None else 3)), "flat_adamw_ex: hyper holds 3 (with ema: 4) fp32 values"
+    assert scaler is None or (scaler.dtype == torch.float32 and scaler.numel() == 4), "flat_adamw_ex: scaler is fp32[4]"
+    assert stats is None or (stats.dtype == torch.float32 and stats.numel() == 4), "flat_adamw_ex: stats is fp32[4]"
+    a = _lib.FlatAdamwExArgs(p=_p(p), g=_p(g), m=_p(m), v=_p(v), ema=_p(ema), n=p.numel(), lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+                             weight_decay=weight_decay, grad_scale=grad_scale, step=step, ema_decay=ema_decay, hyper=_p(hyper),
+                             scaler=_p(scaler), stats=_p(stats))
+    _lib.check(lib.mphsir_flat_adamw_ex(ctypes.byref(a), _stream(p)), "flat_adamw_ex")
+    _acct("flat_adamw_ex", 0.0, (28.0 if ema is None else 36.0) * p.numel())
+    bump_weight_epoch()
+
+
+def grad_check(g, scaler):
+    """scaler[2] = 1 when g holds an inf or a NaN (the first launch of scaled_adamw_step, on its own)"""
+    _check(g, scaler)
+    _lib.check(_lib.load().mphsir_grad_check(_p(g), g.numel(), _p(scaler), _stream(g)), "grad_check")
+
+
+def scaler_update(scaler, growth=2.0, backoff=0.5, interval=2000):
+    """GradScaler.update() on the device state (the last launch of scaled_adamw_step, on its own)"""
+    _check(scaler)
+    _lib.check(_lib.load().mphsir_scaler_update(_p(scaler), growth, backoff, interval, _stream(scaler)), "scaler_update")
+
+
 def dwconv3x3(x, w9, flip=False, out=None):
     """x (B,H,W,C) channels-last (last dim contiguous, row pitch = stride of W axis); w9 fp32 [9][C] view.
     out: optional (B,H,W,C) view to write (a channel slice of a wider buffer: its pixel pitch is passed on) instead of a new tensor."""

@@ -6,7 +6,7 @@ options.py (options.py:6-37), so its command lines (README.md:36,38) work unchan
 Like the reference, the namespace is built at import time (`from options import options as opt`);
 unknown flags are tolerated so that importing this module under pytest/torchrun does not abort.
 Additions (not present in the reference, all optional): --model, --precision, --steps_per_epoch, --graph,
---synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade, --scene_dir, --crop_jitter.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
+--synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade, --scene_dir, --crop_jitter, --grad_clip, --ema_decay.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
 into ['0','1'] (options.py:36) and `--classifier type=bool` treats any non-empty string as True.
 --fused_degrade 1 works at every --patch_size: a patch of up to 128 x 128 is degraded by the plane form of the launch, a larger one (256
 out of a --scene_dir store, say) by its tiled form, with the same plan and the same element values.
@@ -57,6 +57,10 @@ _FLAGS = [
     ("--scene_dir", dict(type=str, default="", help="with --synthetic 0: a directory of .mat / .npy cubes; the scene pyramid is built once, kept in "
                          "HBM, and every batch is cut out of it on the device (scene_store.SceneStore); excludes --db_path")),
     ("--crop_jitter", dict(type=int, default=0, help="1 (with --scene_dir): move every patch origin by a uniform offset below its level's stride")),
+    ("--grad_clip", dict(type=float, default=0.0, help="> 0: clip the global L2 norm of the gradient to this value (clip_grad_norm_'s rule, on the "
+                         "device; a step with a non-finite norm is skipped); 0 (default): off")),
+    ("--ema_decay", dict(type=float, default=0.0, help="> 0: keep an exponential moving average of the weights with this decay (warmed up as "
+                         "min(decay, (1 + t) / (10 + t))), saved as `state_dict_ema` and evaluated by test.py --use_ema 1; 0 (default): off")),
 ]
 
 

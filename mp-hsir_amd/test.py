@@ -93,6 +93,8 @@ def build_parser():
                    "flips and rotations; needs square tiles) transformed restorations of every tile, mapped back; 1: off")
     p.add_argument("--fused_degrade", type=int, default=0, help="1: degrade every cube of modes 0-10 in one HIP launch (degrade.SceneDegrader; no "
                    "Poisson mode 11); 0 (default): the tensor programs of degrade.py")
+    p.add_argument("--use_ema", type=int, default=0, help="1: evaluate the EMA weights of the checkpoint (`state_dict_ema`, written by train.py "
+                   "--ema_decay) instead of `state_dict`; a checkpoint without them ends the run")
     p.add_argument("--save_restored", type=int, default=0, help="1: write <output_path>/<mode label>/restored_<name>.npy (fp32, (C,H,W))")
     return p
 
@@ -277,6 +279,15 @@ def evaluate_quality(o, net, dev):
     return ps / max(n, 1), ss / max(n, 1), (sa / max(n, 1) if fused else None), n
 
 
+def checkpoint_weights(ckpt, use_ema=False, path="the checkpoint"):
+    """the network's state_dict out of a loaded checkpoint (`net.` prefix removed, the reference's test.py:575); use_ema: the averaged
+    weights train.py --ema_decay saved beside them -- a checkpoint without any ends the run with a message"""
+    key = "state_dict_ema" if use_ema else "state_dict"
+    if key not in ckpt:
+        raise SystemExit("--use_ema 1: %s holds no state_dict_ema (it was not trained with --ema_decay)" % path)
+    return {k[4:]: v for k, v in ckpt[key].items() if k.startswith("net.")}
+
+
 def main():
     o = build_parser().parse_args()
     torch.manual_seed(o.seed)
@@ -286,11 +297,13 @@ def main():
         dict(in_channel=100, out_channel=100, dim=96, task_classes=7)
     clip_prompt = "surrogate" if o.allow_surrogate_clip else None
     ckpt = torch.load(o.ckpt_path, map_location="cpu") if o.ckpt_path else None
+    if o.use_ema and ckpt is None:
+        raise SystemExit("--use_ema 1 needs --ckpt_path")
     if ckpt is not None and ckpt.get("mphsir_clip_prompt") is not None:
         clip_prompt = ckpt["mphsir_clip_prompt"]          # the table the checkpoint was trained with
     net = MP_HSIR_Net(**cfg, clip_prompt=clip_prompt, compute_dtype=torch.float32 if o.precision == "f32" else torch.bfloat16).to(dev).eval()
     if ckpt is not None:
-        net.load_state_dict({k[4:]: v for k, v in ckpt["state_dict"].items() if k.startswith("net.")}, strict=False)   # test.py:575
+        net.load_state_dict(checkpoint_weights(ckpt, bool(o.use_ema), o.ckpt_path), strict=False)   # test.py:575
         print("CKPT name : {}".format(o.ckpt_path))
     p, s, sam, n = evaluate_quality(o, net, dev)
     print((MODE_LABEL[o.mode] % vars(o)) + ": psnr: %.2f, ssim: %.4f" % (p, s) + ("" if sam is None else ", sam: %.3f" % sam))

@@ -75,16 +75,20 @@ def load_warm_start(net, path, device, engine=None, resume=False):
         if engine is None or "mphsir_optimizer" not in ckpt:
             raise RuntimeError("--resume 1 needs a checkpoint written by this script (optimizer state); %s has none"
                                % (path if not isinstance(path, dict) else "this one"))
-        engine.load_optimizer_state(ckpt["mphsir_optimizer"])
+        engine.load_optimizer_state(ckpt["mphsir_optimizer"])          # with --ema_decay: the EMA too (a state without one starts it from the weights)
         resume_epoch = int(ckpt.get("epoch", -1)) + 1
     return len(kept), resume_epoch
 
 
 def save_checkpoint(path, net, engine, epoch):
-    """Lightning-compatible layout (`state_dict` with the `net.` prefix, `epoch`) + what resuming needs."""
-    torch.save({"state_dict": {"net." + k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, "epoch": epoch,
-                "mphsir_optimizer": engine.optimizer_state(), "mphsir_clip_prompt": net.clip_prompts.detach().cpu().clone(),
-                "mphsir_clip_source": net.text_prompt.clip_source}, path)
+    """Lightning-compatible layout (`state_dict` with the `net.` prefix, `epoch`) + what resuming needs; with EMA weights on,
+    `state_dict_ema` holds them in the same layout (test.py --use_ema 1)."""
+    ckpt = {"state_dict": {"net." + k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, "epoch": epoch,
+            "mphsir_optimizer": engine.optimizer_state(), "mphsir_clip_prompt": net.clip_prompts.detach().cpu().clone(),
+            "mphsir_clip_source": net.text_prompt.clip_source}
+    if getattr(engine, "ema_decay", None) is not None:
+        ckpt["state_dict_ema"] = {"net." + k: v.detach().cpu().clone() for k, v in engine.ema_state_dict().items()}
+    torch.save(ckpt, path)
 
 
 def main():
@@ -105,7 +109,9 @@ def main():
         clip_prompt = saved if saved is not None else clip_prompt
     dtypes = {"bf16": torch.bfloat16, "f32": torch.float32, "f16": torch.float16}
     net = MP_HSIR_Net(**cfg, clip_prompt=clip_prompt, compute_dtype=dtypes[opt.precision]).to(dev).train()
-    eng = DataParallelEngine(net, lr=opt.lr, use_graph=bool(opt.graph))
+    extras = opt.grad_clip > 0 or opt.ema_decay > 0
+    eng = DataParallelEngine(net, lr=opt.lr, use_graph=bool(opt.graph), grad_clip=opt.grad_clip if opt.grad_clip > 0 else (float("inf") if extras else None),     # EMA alone: measure the norm for the log
+                             ema_decay=opt.ema_decay if opt.ema_decay > 0 else None)
     start_epoch = 0
     if opt.ckpt_path is not None:
         n, start_epoch = load_warm_start(net, ckpt, dev, eng, resume=bool(opt.resume))
@@ -157,7 +163,10 @@ def main():
                 if world > 1:
                     dist.all_reduce(loss, op=dist.ReduceOp.AVG)       # self.log(..., sync_dist=True), train.py:65
                 running = float(loss)
-                if rank == 0:
+                if rank == 0 and extras:
+                    gst = eng.grad_stats()          # one small read-back per logged step (the norm is the unclipped one)
+                    print("epoch %d it %d lr %.3e grad_norm %.4f clip %.3f train_loss %.5f" % (epoch, it + 1, lr, gst["norm"], gst["coef"], running), flush=True)
+                elif rank == 0:
                     print("epoch %d it %d lr %.3e train_loss %.5f" % (epoch, it + 1, lr, running), flush=True)
         if rank == 0 and opt.ckpt_dir and (epoch + 1) % 50 == 0:      # ModelCheckpoint(every_n_epochs=50), train.py:104
             os.makedirs(opt.ckpt_dir, exist_ok=True)
