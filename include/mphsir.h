@@ -792,6 +792,50 @@ typedef struct mphsir_patch_sample_args {
 int64_t mphsir_patch_sample_workspace_bytes(int32_t B, int32_t C);
 int mphsir_patch_sample(const mphsir_patch_sample_args* a, void* stream);
 
+/* ---- coded-aperture snapshot measurement (CASSI) of a clean batch: one launch pair --------------------------------------------------------
+ * The reference's Degradation._sd_cassi (utils/degradation_utils.py:202-225), the measurement of its "unseen task" (task_classes == 1).
+ * With a clean cube x [C][H][W], a mask M [MH][MW], a crop origin (my, mx), a dispersion step s and Wm = W + (C - 1) s:
+ *   mod[c,y,x] = x[c,y,x] * M[my+y, mx+x]                          a rounded product (never contracted with the add below)
+ *   meas[y,u]  = ((0 + mod[0,y,u]) + mod[1,y,u-s]) + ... + mod[C-1,y,u-(C-1)s]     ascending c, fp32 adds; a term with u - c s outside
+ *                                                                  [0, W) is +0 (skipped: the running sum is never -0)
+ *   out[c,y,x] = meas[y, x + c s];   lo, hi = min, max of meas (= of out: every u is covered)
+ *   degraded   = mode_aug[b]((out - lo) / (hi - lo))               two subtractions, one correctly rounded division
+ *   clean_aug  = mode_aug[b](clean[b])                             a bitwise copy, written only when clean_aug != NULL
+ * equal, as floats, to what numpy gives for the reference's lines on the fp32 cube and mask (mp-hsir_amd/degrade.py::cassi_measure is
+ * the tensor form).  A NaN anywhere in a sample's measurement makes that whole sample NaN (as np.min does), a constant measurement is
+ * all NaN (0 / 0), +-inf follow IEEE arithmetic.  mode_m as for mphsir_degrade_batch / mphsir_scene_gather_d4.
+ *   clean, degraded, clean_aug: [B][C][H][W] fp32, contiguous, distinct.  mask: DEVICE fp32 [MH][MW], MH >= H, MW >= W.
+ *   origin  DEVICE int32 [B][2] {my, mx}: clamped into [0, MH - H] x [0, MW - W]; NULL: (0, 0) for every sample
+ *   task    DEVICE int32 [B], optional: only the samples with task[b] == task_id are processed; a workgroup of any other sample returns
+ *           at once and touches neither output of that sample (a mixed degradation menu without a host synchronisation)
+ *   aug     DEVICE int32 [B], optional: the low three bits are the mode; NULL: mode 0; must be NULL when H != W
+ * Nothing the kernels address depends on the contents of origin / task / aug.  Launch 1: one workgroup per (sample, 4 measurement
+ * rows) writes meas [B][H][Wm] and its block's {min, max} (both NaN when the block holds a NaN) to the workspace; launch 2: one
+ * workgroup per (sample, band, 32 output rows) combines its sample's pairs, reads meas back (L2) at the source position of every
+ * output pixel under the inverse of the mode and writes whole rows: 16-byte stores when W % 4 == 0 and the cubes are 16-byte aligned,
+ * element-wise ones otherwise.  No atomics, no zero-fill, nothing read back by the host: bitwise reproducible and capturable; a
+ * captured pair replays with whatever clean / origin / task / aug hold then.
+ * workspace: mphsir_cassi_workspace_bytes(B, C, H, W, step) = 4 (round_up(B H Wm, 4) + 2 B ceil(H / 4)) bytes, 16-byte aligned; the
+ *   query returns a negative value for the shapes the call refuses.
+ * MPHSIR_EINVAL, nothing launched: another struct_size, a null clean / mask / degraded / workspace, B or C outside 1..65535, H * W,
+ *   H * Wm or MH * MW >= 2^31, B * C >= 2^31, MH < H or MW < W, step outside 1..8, aug != NULL with H != W, a workspace that is too
+ *   small or not 16-byte aligned, degraded == clean (or clean_aug equal to either).  Element offsets are 64-bit.                      */
+typedef struct mphsir_cassi_args {
+    uint32_t struct_size;
+    const float* clean;
+    const float* mask;
+    const int32_t* origin;
+    const int32_t* task;
+    const int32_t* aug;
+    float* degraded;
+    float* clean_aug;
+    void* workspace;
+    int64_t workspace_bytes;
+    int32_t B, C, H, W, MH, MW, step, task_id;
+} mphsir_cassi_args;
+int64_t mphsir_cassi_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t step);
+int mphsir_cassi(const mphsir_cassi_args* a, void* stream);
+
 /* ---- fused AdamW over the flat parameter arena ---------------------------------------------------
  * One decoupled-weight-decay Adam step on n contiguous fp32 parameters (n % 4 == 0) with gradient g,
  * moments m, v; g is multiplied by grad_scale first (1/world_size after a sum all-reduce).
@@ -945,7 +989,9 @@ int mphsir_l1_clamp_loss(const float* y, const float* clean, float* grad, float*
 #define MPHSIR_K_DEGRADE 34
 #define MPHSIR_K_PATCH_SAMPLE 35      /* launch 1 of mphsir_patch_sample (min / max per plane) */
 #define MPHSIR_K_PATCH_NORMALISE 36   /* launch 2 (combine + normalise): ids of their own, so that the timer tells the two apart */
-#define MPHSIR_K_COUNT 37
+#define MPHSIR_K_CASSI_MEASURE 37     /* launch 1 of mphsir_cassi (measurement rows + block min / max) */
+#define MPHSIR_K_CASSI_EMIT 38        /* launch 2 (combine + normalise + flip / rotation) */
+#define MPHSIR_K_COUNT 39
 int mphsir_prof_enable(int kid);   /* kid < 0 disables */
 int mphsir_prof_read(int* launches, float* total_ms);
 const char* mphsir_kernel_name(int kid);

@@ -176,6 +176,12 @@ class PatchSampleArgs(_Args):
                [("workspace_bytes", c_int64), ("arena_elems", c_int64)] + [(n, c_int32) for n in ("n_levels", "n_records", "B", "C", "P")]
 
 
+class CassiArgs(_Args):
+    """mirror of struct mphsir_cassi_args"""
+    _fields_ = _SZ + [(n, c_void_p) for n in ("clean", "mask", "origin", "task", "aug", "degraded", "clean_aug", "workspace")] + \
+               [("workspace_bytes", c_int64)] + [(n, c_int32) for n in ("B", "C", "H", "W", "MH", "MW", "step", "task_id")]
+
+
 # The two optimizer structs hold float members; tests/test_optim_ex_meta.py compares them with include/mphsir.h field by field.
 class GradNormArgs(_Args):
     """ctypes image of mphsir_grad_norm_args"""
@@ -302,6 +308,8 @@ _SYMBOLS = {
     "mphsir_degrade_planes": (c_int, [ctypes.POINTER(DegradeArgs), c_void_p]),
     "mphsir_patch_sample_workspace_bytes": (c_int64, [c_int32, c_int32]),
     "mphsir_patch_sample": (c_int, [ctypes.POINTER(PatchSampleArgs), c_void_p]),
+    "mphsir_cassi_workspace_bytes": (c_int64, [c_int32] * 5),
+    "mphsir_cassi": (c_int, [ctypes.POINTER(CassiArgs), c_void_p]),
     "mphsir_l1_clamp_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
 }
 

@@ -22,15 +22,16 @@ class SyntheticPatchSource:
     degrade.DegradationSynthesizer, task id = index of the degradation applied (as ImageTransformDataset does)."""
 
     def __init__(self, bands=31, patch=64, batch=32, task_classes=6, device="cuda", seed=2024, rank=0, de_types=None,
-                 data_type="natural_scene", pool=0, fused_degrade=False):
+                 data_type="natural_scene", pool=0, fused_degrade=False, cassi=None):
         # pool = n > 0: the first n batches are generated once and handed out round-robin afterwards -- the inputs of a timed run are
         # then resident in HBM before the timed region starts (the reference's loader workers run beside the GPU, not on it)
         self.pool, self._pooled, self._turn = pool, [], 0
         self.shape = (batch, bands, patch, patch)
         self.task_classes, self.device = task_classes, device
         self.gen = torch.Generator(device=device).manual_seed(seed + 7919 * rank)
+        # cassi: dict(cassi_mask=degrade.CassiMask, cassi_step=int) for a menu with 'cassi' (None: the default mask, step 2)
         # fused_degrade: the synthesiser's one-launch path (degrade.DegradationSynthesizer(fused=True)); off = the tensor programs
-        self.syn = degrade.DegradationSynthesizer(data_type, de_types, device, seed + 7919 * rank + 1, fused=fused_degrade) if de_types else None
+        self.syn = degrade.DegradationSynthesizer(data_type, de_types, device, seed + 7919 * rank + 1, fused=fused_degrade, **(cassi or {})) if de_types else None
 
     def next(self):
         if self.pool:
@@ -121,11 +122,11 @@ class PatchDBSource:
     (dataset_utils.py:131-132), and degrade.DegradationSynthesizer produces (degraded, clean, prompt) on the device.
     Each rank walks its own seeded permutation (DistributedSampler-style shard: index = perm[rank::world])."""
 
-    def __init__(self, db, batch, de_types, data_type, device, seed=2024, rank=0, world=1, repeat=1, fused_degrade=False):
+    def __init__(self, db, batch, de_types, data_type, device, seed=2024, rank=0, world=1, repeat=1, fused_degrade=False, cassi=None):
         self.db, self.batch, self.device, self.data_type = db, batch, torch.device(device), data_type
         self.rank, self.world, self.repeat = rank, world, repeat
         self.rng = np.random.RandomState(seed)                       # same permutation on every rank, then sharded
-        self.syn = degrade.DegradationSynthesizer(data_type, de_types, device, seed + 7919 * rank + 1, fused=fused_degrade)
+        self.syn = degrade.DegradationSynthesizer(data_type, de_types, device, seed + 7919 * rank + 1, fused=fused_degrade, **(cassi or {}))
         self.order, self.pos, self._copied = None, 0, None
         c, h, w = db.records[0][1]
         self.stage = torch.empty((batch, c, h, w), dtype=torch.float32)
@@ -170,11 +171,11 @@ class SceneStoreSource:
     that touches the mask falls back to the record's own origin (four look-ups in the mask level's integral image, merged with
     torch.where).  The reference cannot do this; off by default.  `last_origins` gives the (B,3) int32 {level, y, x} of the last batch."""
 
-    def __init__(self, store, batch, de_types, data_type, device, seed=2024, rank=0, world=1, repeat=1, fused_degrade=False, jitter=False):
+    def __init__(self, store, batch, de_types, data_type, device, seed=2024, rank=0, world=1, repeat=1, fused_degrade=False, jitter=False, cassi=None):
         self.store, self.batch, self.device, self.data_type = store, batch, torch.device(device), data_type
         self.rank, self.world, self.repeat, self.jitter = rank, world, repeat, bool(jitter)
         self.rng = np.random.RandomState(seed)                       # same permutation on every rank, then sharded
-        self.syn = degrade.DegradationSynthesizer(data_type, de_types, device, seed + 7919 * rank + 1, fused=fused_degrade)
+        self.syn = degrade.DegradationSynthesizer(data_type, de_types, device, seed + 7919 * rank + 1, fused=fused_degrade, **(cassi or {}))
         self.order, self.order_dev, self.pos, self._pin = None, None, 0, None
         self.gen = torch.Generator(device=self.device).manual_seed(seed + 7919 * rank + 2) if self.jitter else None
         self._last = None

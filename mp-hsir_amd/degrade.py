@@ -28,7 +28,7 @@ import torch.nn.functional as F
 DE_DICT = {
     "natural_scene": {"gaussianN": [(30, 70)], "complexN": [(10, 30, 50, 70), (0.05, 0.15), (0.1, 0.3, 0.5, 0.7), (0.05, 0.15)],
                       "blur": [(9, 15, 21)], "sr": [(2, 4, 8)], "inpaint": [(0.7, 0.8, 0.9)], "bandmiss": [(0.1, 0.2, 0.3)],
-                      "motion_blur": [((15, 45),)]},
+                      "motion_blur": [((15, 45),)], "cassi": [(0,)]},
     "remote_sensing": {"gaussianN": [(30, 70)], "complexN": [(10, 30, 50, 70), (0.05, 0.15), (0.1, 0.3, 0.5, 0.7), (0.05, 0.15)],
                        "blur": [(7, 11, 15)], "sr": [(2, 4, 8)], "inpaint": [(0.7, 0.8, 0.9)], "haze": [(0.5, 0.75, 1)],
                        "bandmiss": [(0.1, 0.2, 0.3)], "circle_blur": [(9,)], "poissonN": [(10,)]},
@@ -167,6 +167,84 @@ def poisson_noise(x, scale, generator=None):
     return torch.poisson(x.clamp_min(0) * scale, generator=generator) / scale
 
 
+def cassi_measure(x, mask, origin=None, step=2):
+    """_sd_cassi (:202-225), the coded-aperture snapshot measurement, and the DEFINITION of what csrc/cassi.hip computes: x (B,C,H,W) fp32,
+    mask (MH,MW) fp32, origin (B,2) integer {my, mx} of the mask crop (clamped into the mask; None: (0,0)).  Every band is multiplied by the
+    crop, moved `step` columns further per band and added to the measurement in ASCENDING band order (an explicit loop: the order of a
+    sum(dim) is not ours to fix); band c of the result is the measurement's window at c * step; the whole sample is min-max normalised over
+    its measurement.  A NaN in the measurement makes the sample NaN, a constant measurement is all NaN (0 / 0)."""
+    B, C, H, W = x.shape
+    MH, MW = mask.shape
+    if MH < H or MW < W:
+        raise ValueError("cassi: a mask of %d x %d does not hold a plane of %d x %d" % (MH, MW, H, W))
+    mask = mask.to(x.device, torch.float32)
+    if origin is None:
+        crop = mask[:H, :W].expand(B, H, W)
+    else:
+        origin = torch.as_tensor(origin, device=x.device).reshape(B, 2).long()
+        my, mx = origin[:, 0].clamp(0, MH - H), origin[:, 1].clamp(0, MW - W)
+        rows = my[:, None] + torch.arange(H, device=x.device)
+        cols = mx[:, None] + torch.arange(W, device=x.device)
+        crop = mask[rows[:, :, None], cols[:, None, :]]                                   # (B,H,W)
+    meas = torch.zeros((B, H, W + (C - 1) * step), dtype=x.dtype, device=x.device)
+    for c in range(C):
+        meas[:, :, step * c:step * c + W] += x[:, c] * crop
+    out = torch.stack([meas[:, :, step * c:step * c + W] for c in range(C)], dim=1)
+    lo, hi = meas.amin(dim=(1, 2)).reshape(B, 1, 1, 1), meas.amax(dim=(1, 2)).reshape(B, 1, 1, 1)
+    return (out - lo) / (hi - lo)
+
+
+class CassiMask:
+    """The coded aperture of the cassi task, resident on the device as fp32 (cast once, here): the 'mask' entry of a .mat file (as the
+    reference reads it, degradation_utils.py:209-210), a .npy file, or -- path None -- a seeded Bernoulli(0.5) binary mask of `shape`.
+    origins(): the per-sample crop origins, random.randint(0, MH - H) / (0, MW - W) in the reference (:211-212), from a Draws."""
+
+    def __init__(self, device, path=None, seed=2024, shape=(256, 256)):
+        if path is None:
+            g = torch.Generator().manual_seed(int(seed))
+            m = (torch.rand(tuple(shape), generator=g) < 0.5).to(torch.float32)
+        elif str(path).endswith(".npy"):
+            import numpy as np
+            m = torch.from_numpy(np.load(path).astype("float32"))
+        else:
+            import scipy.io as sio
+            m = torch.from_numpy(sio.loadmat(path)["mask"].astype("float32"))
+        if m.dim() != 2:
+            raise ValueError("cassi mask %s: a 2-D array is expected, got shape %s" % (path, tuple(m.shape)))
+        self.path = path
+        self.mask = m.contiguous().to(device)
+
+    @property
+    def shape(self):
+        return tuple(self.mask.shape)
+
+    def check(self, H, W):
+        MH, MW = self.shape
+        if MH < H or MW < W:
+            raise ValueError("cassi mask %s of %d x %d is smaller than the %d x %d plane it has to cover" % (self.path or "(default)", MH, MW, H, W))
+
+    def origins(self, d, B, H, W):
+        """(B,2) int32 {my, mx} on the device, from the Draws d"""
+        self.check(H, W)
+        MH, MW = self.shape
+        return torch.stack([d.randint(0, MH - H + 1, (B,)), d.randint(0, MW - W + 1, (B,))], dim=1).to(torch.int32).contiguous()
+
+
+_SCENE_MASKS = {}
+
+
+def scene_cassi_mask(opts, device, H, W):
+    """the CassiMask of test.py's mode 13 for a cube of H x W (made once per file / extent): --cassi_mask, or the default mask of
+    max(256, H) x max(256, W) seeded by --seed.  ValueError when the file's mask is smaller than the cube."""
+    path = getattr(opts, "cassi_mask", "") or None
+    shape = (max(256, H), max(256, W))
+    key = (path, str(device)) if path else (None, str(device), int(opts.seed), shape)
+    if key not in _SCENE_MASKS:
+        _SCENE_MASKS[key] = CassiMask(device, path, seed=opts.seed, shape=shape)
+    _SCENE_MASKS[key].check(H, W)
+    return _SCENE_MASKS[key]
+
+
 def augment(x, mode):
     """data_augmentation (utils/image_utils.py:141-176) per sample: mode (B,) in 0..7 = rot90 by mode//2 (counter-clockwise,
     axes (H,W)) then an up-down flip when mode is odd.  Square patches."""
@@ -259,12 +337,14 @@ class DegradationSynthesizer:
     applied to both cubes; emits `degrad_patch, clean_patch, prompt (B,1) int64`.  `cirrus` (a callable (B,H,W) -> maps in
     [0,1]) supplies the haze maps the reference reads from .mat files (:245-257); default: smooth synthetic fields."""
 
-    def __init__(self, data_type, de_types, device, seed=2024, cirrus=None, fused=False):
+    def __init__(self, data_type, de_types, device, seed=2024, cirrus=None, fused=False, cassi_mask=None, cassi_step=2):
         self.table, self.de_types = DE_DICT[data_type], list(de_types)
         for t in self.de_types:
             if t not in self.table:
                 raise ValueError("degradation %r is not defined for %s" % (t, data_type))
         self.d = Draws(device, seed)
+        self.cassi_step = int(cassi_step)
+        self.cassi_mask = cassi_mask if cassi_mask is not None or "cassi" not in self.de_types else CassiMask(device, seed=seed)
         self.cirrus = cirrus or self._synthetic_cirrus
         self.fused = bool(fused)
         if self.fused:
@@ -310,6 +390,8 @@ class DegradationSynthesizer:
             return haze(x, self.cirrus(B, H, W), d.choice(list(rng[0]), B))
         if de_type == "poissonN":
             return poisson_noise(x, float(rng[0][0]), generator=d.gen)
+        if de_type == "cassi":
+            return cassi_measure(x, self.cassi_mask.mask, self.cassi_mask.origins(d, B, H, W), self.cassi_step)
         raise ValueError("Invalid degradation type " + de_type)
 
     # ---- fused=True: a plan of small device tables (batched tensor ops, no host synchronisation) + ONE launch (csrc/degrade.hip) ----
@@ -359,7 +441,7 @@ class DegradationSynthesizer:
         de_id = d.randint(0, len(self.de_types), (B,))
         param = torch.zeros((B,), dtype=torch.float32, device=dev)
         sub = torch.zeros((B,), dtype=torch.int64, device=dev)
-        tabs, flag = {}, None
+        tabs, flag, origin = {}, None, None
         for t, name in enumerate(self.de_types):
             rng, mine = self.table[name], de_id == t
             if name == "gaussianN":
@@ -399,21 +481,34 @@ class DegradationSynthesizer:
                     lam = torch.linspace(400, 1000, 100, device=dev, dtype=torch.float64)[:C]
                     self._haze_ratio[C] = (lam[0] / lam).to(torch.float32)
                 tabs["haze_ratio"] = self._haze_ratio[C]
+            elif name == "cassi":
+                origin = self.cassi_mask.origins(d, B, H, W)
         if flag is not None:
             tabs["band_flag"] = flag.to(torch.uint8)
         plan = ops.DegradePlan(self._menu, self._ksize, self._factors, task=de_id.to(torch.int32), aug=d.randint(1, 8, (B,)).to(torch.int32),
                                param=param, sub=sub.to(torch.int32), stencils=self._stencils, **tabs)
+        plan.cassi_origin = origin                  # not a table of the degradation launch: ops.cassi reads it (None without cassi in the menu)
         return plan, de_id
 
     def _call_fused(self, clean):
         from . import ops
         clean = clean.contiguous()
         plan, de_id = self.fused_plan(clean)
+        cassi = self.de_types.index("cassi") if "cassi" in self.de_types else -1
+        if cassi >= 0 and len(self.de_types) == 1:
+            # the fine-tune menu: the cassi pair alone, which writes the augmented clean cube itself
+            degraded, clean_aug = ops.cassi(clean, self.cassi_mask.mask, plan.cassi_origin, self.cassi_step, aug=plan.aug, want_clean_aug=True)
+            return degraded, clean_aug, de_id.reshape(-1, 1)
         self._ordinal += 1                                                               # the batch ordinal counts calls, on the device
         # planes that fit in LDS whole keep the plane form's launch; larger ones go through the tiled form, which computes the same values
         H, W = clean.shape[-2:]
         fn = ops.degrade_batch if H * W <= 128 * 128 else ops.degrade_planes
         degraded, clean_aug = fn(clean, plan, seed=self.seed, ordinal=self._ordinal)
+        if cassi >= 0:
+            # cassi is kind `none` in that launch's menu (its samples left it as augmented copies); the pair overwrites exactly them,
+            # selected on the device by the task table: no nonzero / item / boolean indexing
+            ops.cassi(clean, self.cassi_mask.mask, plan.cassi_origin, self.cassi_step, aug=plan.aug, task=plan.task, task_id=cassi,
+                      out=(degraded, None))
         return degraded, clean_aug, de_id.reshape(-1, 1)
 
     def __call__(self, clean):
@@ -436,7 +531,8 @@ class SceneDegrader:
     temporary, no library convolution, and a result that depends on (seed, cube ordinal, the plan) only -- the per-element draws are the
     launch's Philox draws keyed by the seed and the ordinal, which counts calls; the plan's small tables (per-band sigmas, band and column
     subsets, the cirrus map) come from a seeded torch.Generator with the expressions of test.py::degrade_for_mode.  `opts`: test.py's
-    parsed flags.  Mode 11 (Poisson) has no fused form, mode 12 degrades nothing."""
+    parsed flags.  Mode 11 (Poisson) has no fused form, mode 12 degrades nothing.  Mode 13 (the CASSI measurement) is the launch pair of
+    ops.cassi with the mask of scene_cassi_mask and the origin test.py::degrade_for_mode draws: the tensor form's values."""
     PROMPT = {0: 0, 1: 1, 2: 1, 3: 1, 4: 1, 5: 2, 6: 0, 7: 3, 8: 4, 9: 5, 10: 5}
 
     def __init__(self, model, device, seed):
@@ -446,6 +542,8 @@ class SceneDegrader:
         self._stencils, self._haze_ratio, self._consts = {}, {}, {}
 
     def prompt_id(self, mode):
+        if mode == 13:
+            return 0
         return 6 if mode == 10 and self.model != "natural_scene" else self.PROMPT[mode]
 
     def _const(self, shape, dtype, value, dev):
@@ -542,6 +640,10 @@ class SceneDegrader:
         """clean (1,C,H,W) fp32 on the device -> (degraded, prompt id): the plan, then one launch; no copy of the clean cube is written"""
         from . import ops
         clean = clean.contiguous()
+        if mode == 13:
+            B, _, H, W = clean.shape
+            mask = scene_cassi_mask(opts, clean.device, H, W)
+            return ops.cassi(clean, mask.mask, mask.origins(self.d, B, H, W), opts.cassi_step)[0], 0
         plan = self.plan(clean, mode, opts)
         self.ordinal += 1
         return ops.degrade_planes(clean, plan, seed=self.seed, ordinal=self.ordinal, want_clean=False)[0], self.prompt_id(mode)

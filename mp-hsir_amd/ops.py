@@ -773,7 +773,8 @@ def quality_bands(restored, clean):
 
 
 DEG_KINDS = {"none": 0, "gaussianN": 1, "complexN": 2, "blur": 3, "motion_blur": 3, "circle_blur": 3, "sr": 4, "inpaint": 5, "bandmiss": 6,
-             "haze": 7}             # MPHSIR_DEG_* of include/mphsir.h (every blur is a stencil); poissonN has no fused form
+             "haze": 7, "cassi": 0} # MPHSIR_DEG_* of include/mphsir.h (every blur is a stencil); poissonN has no fused form; cassi is `none`
+                                    # in that launch: its samples are overwritten by the launch pair of ops.cassi
 _DEG_TABLES = (("task", torch.int32, "b"), ("aug", torch.int32, "b"), ("param", torch.float32, "b"), ("sub", torch.int32, "b"),
                ("band_sigma", torch.float32, "bc"), ("band_flag", torch.uint8, "bc"), ("col_dead", torch.uint8, "bcn"),
                ("col_off", torch.float32, "bcn"), ("stencils", torch.float32, "k"), ("cirrus", torch.float32, "bnn"),
@@ -877,6 +878,43 @@ def patch_sample(arena, levels, levels_host, records, index, C, P, out=None, wor
                              n_levels=levels.shape[0], n_records=records.shape[0], B=B, C=C, P=P)
     _lib.check(lib.mphsir_patch_sample(ctypes.byref(a), _stream(arena)), "patch_sample")
     _acct("patch_sample", 0.0, 12.0 * out.numel())
+    return out
+
+
+def cassi(clean, mask, origin=None, step=2, aug=None, task=None, task_id=0, want_clean_aug=False, out=None, workspace=None):
+    """The coded-aperture snapshot measurement of a batch (mphsir_cassi, include/mphsir.h; degrade.cassi_measure is the tensor form): clean
+    (B,C,H,W) fp32, mask (MH,MW) fp32 on the device, origin (B,2) int32 {my, mx} (clamped by the kernel; None: (0,0)), aug (B,) int32 modes
+    of degrade.augment (None: mode 0; must be None when H != W), task (B,) int32 with task_id: only the samples with task[b] == task_id are
+    processed, the others keep what `out` held.  -> (degraded, clean_aug or None); out = (degraded, clean_aug or None) to write into.  One
+    launch pair on the current stream, nothing read back."""
+    lib = _lib.load()
+    _check(clean, mask, origin, aug, task, workspace, *(out or ()))
+    assert clean.dim() == 4 and clean.dtype == torch.float32 and clean.is_contiguous(), "cassi: a contiguous (B,C,H,W) fp32 batch"
+    assert mask.dim() == 2 and mask.dtype == torch.float32 and mask.is_contiguous() and mask.device == clean.device, \
+        "cassi: the mask is a contiguous (MH,MW) fp32 tensor on %s" % clean.device
+    B, C, H, W = clean.shape
+    dev = clean.device
+    assert origin is None or (origin.dtype == torch.int32 and tuple(origin.shape) == (B, 2) and origin.is_contiguous() and origin.device == dev), \
+        "cassi: origin is (B,2) int32"
+    for name, t in (("aug", aug), ("task", task)):
+        assert t is None or (t.dtype == torch.int32 and tuple(t.shape) == (B,) and t.is_contiguous() and t.device == dev), "cassi: %s is (B,) int32" % name
+    nbytes = lib.mphsir_cassi_workspace_bytes(B, C, H, W, int(step))
+    if nbytes < 0:
+        raise RuntimeError("mp-hsir_amd: cassi refuses (B %d, C %d, H %d, W %d, step %d): B, C in 1..65535, step in 1..8, planes below 2^31 elements"
+                           % (B, C, H, W, step))
+    if workspace is None:
+        workspace = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+    assert workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.device == dev
+    if out is None:
+        out = (torch.empty_like(clean), torch.empty_like(clean) if want_clean_aug else None)
+    assert len(out) == 2 and out[0] is not None, "cassi: out = (degraded, clean_aug or None)"
+    for t in out:
+        assert t is None or (t.shape == clean.shape and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev)
+    a = _lib.CassiArgs(clean=_p(clean), mask=_p(mask), origin=_p(origin), task=_p(task), aug=_p(aug), degraded=_p(out[0]), clean_aug=_p(out[1]),
+                       workspace=_p(workspace), workspace_bytes=workspace.numel() * 4, B=B, C=C, H=H, W=W, MH=mask.shape[0], MW=mask.shape[1],
+                       step=int(step), task_id=int(task_id))
+    _lib.check(lib.mphsir_cassi(ctypes.byref(a), _stream(clean)), "cassi")
+    _acct("cassi", 0.0, (12.0 if out[1] is not None else 8.0) * clean.numel())
     return out
 
 

@@ -6,10 +6,12 @@ options.py (options.py:6-37), so its command lines (README.md:36,38) work unchan
 Like the reference, the namespace is built at import time (`from options import options as opt`);
 unknown flags are tolerated so that importing this module under pytest/torchrun does not abort.
 Additions (not present in the reference, all optional): --model, --precision, --steps_per_epoch, --graph,
---synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade, --scene_dir, --crop_jitter, --grad_clip, --ema_decay.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
+--synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade, --scene_dir, --crop_jitter, --grad_clip, --ema_decay, --task_classes, --cassi_mask, --cassi_step.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
 into ['0','1'] (options.py:36) and `--classifier type=bool` treats any non-empty string as True.
 --fused_degrade 1 works at every --patch_size: a patch of up to 128 x 128 is degraded by the plane form of the launch, a larger one (256
 out of a --scene_dir store, say) by its tiled form, with the same plan and the same element values.
+The reference's "unseen task" fine-tune (its task_classes == 1 branch, net/MP_HSIR.py:503-506, and 'cassi' in its menu, dataset_utils.py:112):
+    python train.py --data_type natural_scene --natural_scene_single_de_type cassi --task_classes 1 --ckpt_path ALLINONE.ckpt
 """
 import argparse
 
@@ -59,6 +61,11 @@ _FLAGS = [
     ("--crop_jitter", dict(type=int, default=0, help="1 (with --scene_dir): move every patch origin by a uniform offset below its level's stride")),
     ("--grad_clip", dict(type=float, default=0.0, help="> 0: clip the global L2 norm of the gradient to this value (clip_grad_norm_'s rule, on the "
                          "device; a step with a non-finite norm is skipped); 0 (default): off")),
+    ("--task_classes", dict(type=int, default=0, help="0 (default): the model's own task set (6 natural-scene, 7 remote-sensing); 1: the one-task "
+                            "net of the cassi fine-tune (the warm start drops the tensors whose shapes differ)")),
+    ("--cassi_mask", dict(type=str, default="", help="'cassi' degradation: the coded-aperture mask, a .mat file with a 'mask' entry (as the reference "
+                          "reads it) or a .npy file; default: a seeded Bernoulli(0.5) binary mask of 256 x 256")),
+    ("--cassi_step", dict(type=int, default=2, help="'cassi' degradation: dispersion step in columns per band (the reference: 2)")),
     ("--ema_decay", dict(type=float, default=0.0, help="> 0: keep an exponential moving average of the weights with this decay (warmed up as "
                          "min(decay, (1 + t) / (10 + t))), saved as `state_dict_ema` and evaluated by test.py --use_ema 1; 0 (default): off")),
 ]

@@ -16,6 +16,9 @@ forward under no_grad, band-wise PSNR / SSIM on the device (metrics.py = utils/v
   10    missing bands, scored on the missing bands only (:842-879)         5 (6 RS)   --bandmis_ratio 0.3
   11    Poisson noise scale 10 (:243-275)                                  0
   12    real degraded / clean pairs from --test_degrad_dir (:197-241)      1
+  13    CASSI snapshot measurement of the whole cube (an ADDITION: the     0          --cassi_mask --cassi_step 2
+        reference has the task, degradation_utils.py:202-225, and no
+        test mode for it); for a net built with --task_classes 1
 
 Test cubes: --test_dir with .mat ('data' key, as the reference) or .npy cubes; without it, synthetic cubes (no datasets offline).
 Without --tile every cube is centre-cropped to multiples of 64 (crop_img, utils/image_utils.py:58-70) and restored in one forward,
@@ -32,6 +35,10 @@ one-tile scene of that restorer, which for ensemble 1 is bitwise the plain forwa
 same element values, no cube-sized temporary, no library convolution, draws that depend on --seed and the cube's ordinal only -- other
 random streams than the tensor programs', so other scores within the noise; with or without --tile / --ensemble).  Mode 11 (Poisson
 noise) has no fused form and ends the run with a message; mode 12 degrades nothing and ignores the flag.
+Mode 13 measures the cube through the coded aperture --cassi_mask (a .mat with a 'mask' entry or a .npy; default: a seeded binary mask of
+max(256, H) x max(256, W)) at a crop origin drawn from --seed, with the tensor form (degrade.cassi_measure) or, under --fused_degrade 1,
+the HIP launch pair (ops.cassi): the same values either way, since the measurement has no per-element draws.  A mask file smaller
+than the cube ends the run with a message.
 --ckpt_path evaluates a Lightning checkpoint of the reference (`net.` key prefix).
 """
 import argparse
@@ -95,6 +102,9 @@ def build_parser():
                    "Poisson mode 11); 0 (default): the tensor programs of degrade.py")
     p.add_argument("--use_ema", type=int, default=0, help="1: evaluate the EMA weights of the checkpoint (`state_dict_ema`, written by train.py "
                    "--ema_decay) instead of `state_dict`; a checkpoint without them ends the run")
+    p.add_argument("--task_classes", type=int, default=0, help="0: the model's own task set (6 / 7); 1: the one-task net of the cassi fine-tune (mode 13)")
+    p.add_argument("--cassi_mask", type=str, default="", help="mode 13: coded-aperture mask, a .mat ('mask') or .npy file; default: a seeded binary mask")
+    p.add_argument("--cassi_step", type=int, default=2, help="mode 13: dispersion step in columns per band (the reference: 2)")
     p.add_argument("--save_restored", type=int, default=0, help="1: write <output_path>/<mode label>/restored_<name>.npy (fp32, (C,H,W))")
     return p
 
@@ -176,6 +186,12 @@ def degrade_for_mode(o, clean, d, model):
         return D.band_loss(clean, d.rand(B, C).argsort(dim=1).argsort(dim=1) < n), (5 if model == "natural_scene" else 6)
     if m == 11:
         return D.poisson_noise(clean, 10.0, generator=d.gen), 0
+    if m == 13:
+        try:
+            mask = D.scene_cassi_mask(o, clean.device, H, W)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        return D.cassi_measure(clean, mask.mask, mask.origins(d, B, H, W), o.cassi_step), 0
     raise SystemExit("unknown mode %d" % m)
 
 
@@ -184,7 +200,7 @@ MODE_LABEL = {0: "Denoise sigma=%(gaussian_noise_sigma)s", 1: "Denoise sigma=%(g
               4: "Impulse denoise impulse ratio=%(impulse_nosie_ratio)s", 5: "Gaussian deblur sigma=%(gaussian_blur_radius)s",
               6: "Motion deblur motion radius=%(motion_blur_radius)s", 7: "Super resolution downsample factor=%(downsample_factor)s",
               8: "Inpaint mask ratio=%(mask_ratio)s", 9: "Dehaze haze omega=%(haze_omega)s", 10: "Bandmiss ratio=%(bandmis_ratio)s",
-              11: "Degrad_Id=%(degrad_id)s", 12: "Degrad_Id=%(degrad_id)s"}
+              11: "Degrad_Id=%(degrad_id)s", 12: "Degrad_Id=%(degrad_id)s", 13: "CASSI step=%(cassi_step)s"}
 
 
 def mode_dir(o):
@@ -253,7 +269,12 @@ def evaluate_quality(o, net, dev):
         if o.mode == 12:
             degraded, pid = real, 1
         elif fused_degrader is not None:
-            degraded, pid = fused_degrader(clean, o.mode, o)
+            try:
+                degraded, pid = fused_degrader(clean, o.mode, o)
+            except ValueError as e:
+                if o.mode != 13:
+                    raise
+                raise SystemExit(str(e))                    # a mask file smaller than the cube
         else:
             degraded, pid = degrade_for_mode(o, clean, d, o.model)
         if scenes:
@@ -301,6 +322,8 @@ def main():
         raise SystemExit("--use_ema 1 needs --ckpt_path")
     if ckpt is not None and ckpt.get("mphsir_clip_prompt") is not None:
         clip_prompt = ckpt["mphsir_clip_prompt"]          # the table the checkpoint was trained with
+    if o.task_classes:
+        cfg["task_classes"] = o.task_classes
     net = MP_HSIR_Net(**cfg, clip_prompt=clip_prompt, compute_dtype=torch.float32 if o.precision == "f32" else torch.bfloat16).to(dev).eval()
     if ckpt is not None:
         net.load_state_dict(checkpoint_weights(ckpt, bool(o.use_ema), o.ckpt_path), strict=False)   # test.py:575

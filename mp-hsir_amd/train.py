@@ -27,9 +27,10 @@ import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from mp_hsir_amd import degrade  # noqa: E402
 from mp_hsir_amd.data import REMOTE_SENSING_SOURCES, PatchDB, PatchDBSource, SceneStoreSource, SyntheticPatchSource  # noqa: E402
 from mp_hsir_amd.engine import DataParallelEngine, warmup_cosine_lr  # noqa: E402
-from mp_hsir_amd.net.MP_HSIR import MP_HSIR_Net  # noqa: E402
+from mp_hsir_amd.net.MP_HSIR import _TASK_PROMPTS, MP_HSIR_Net  # noqa: E402
 from mp_hsir_amd.options import options as opt  # noqa: E402
 from mp_hsir_amd.scene_store import SceneStore, scene_files  # noqa: E402
 
@@ -100,7 +101,9 @@ def main():
     if rank == 0:
         print("Options\n", opt)
     set_seed(opt.seed)
-    cfg = MODELS[opt.model or opt.data_type]
+    cfg = dict(MODELS[opt.model or opt.data_type])
+    if opt.task_classes:
+        cfg["task_classes"] = opt.task_classes                           # --task_classes 1: the one-task net of the cassi fine-tune
     clip_prompt = "surrogate" if opt.allow_surrogate_clip else None      # None: encode with OpenAI clip, or raise
     ckpt = None
     if opt.ckpt_path is not None:
@@ -125,9 +128,16 @@ def main():
             raise SystemExit("--resume 1: %s already holds epoch %d of --epochs %d: nothing left to train" % (opt.ckpt_path, start_epoch - 1, opt.epochs))
     data_type = opt.model or opt.data_type
     de_types = opt.natural_scene_single_de_type if data_type == "natural_scene" else opt.remote_sensing_single_de_type
+    cassi = None
+    if "cassi" in de_types:
+        cassi = dict(cassi_mask=degrade.CassiMask(dev, opt.cassi_mask or None, seed=opt.seed), cassi_step=opt.cassi_step)
+        at, sentences = de_types.index("cassi"), net.text_prompt.task_text_prompts             # the prompt id is the index into the menu
+        if rank == 0 and (at >= len(sentences) or sentences[at] != _TASK_PROMPTS["cassi"]):
+            print("warning: 'cassi' is task %d of the menu, and task %d of this net is %s: build the one-task net with --task_classes 1" %
+                  (at, at, repr(sentences[at]) if at < len(sentences) else "missing"), flush=True)
     if opt.synthetic:
         src = SyntheticPatchSource(cfg["in_channel"], opt.patch_size, opt.batch_size, cfg["task_classes"], dev, opt.seed, rank,
-                                   de_types=de_types, data_type=data_type, fused_degrade=bool(opt.fused_degrade))
+                                   de_types=de_types, data_type=data_type, fused_degrade=bool(opt.fused_degrade), cassi=cassi)
         steps_per_epoch = opt.steps_per_epoch
     else:
         if opt.db_path and opt.scene_dir:
@@ -147,11 +157,11 @@ def main():
                 print("scene store: %d records from %d levels, %.1f MB resident, %d degenerate" %
                       (len(store), store.levels_host.shape[0], store.nbytes / 1e6, store.degenerate), flush=True)
             src = SceneStoreSource(store, opt.batch_size, de_types, data_type, dev, opt.seed, rank, world, opt.repeat,
-                                   fused_degrade=bool(opt.fused_degrade), jitter=bool(opt.crop_jitter))
+                                   fused_degrade=bool(opt.fused_degrade), jitter=bool(opt.crop_jitter), cassi=cassi)
         else:
             keep_all = data_type == "natural_scene" or opt.all_sources          # dataset_utils.py:56 filters remote-sensing sources
             db = PatchDB(opt.db_path, dataset_names=None if keep_all else REMOTE_SENSING_SOURCES)
-            src = PatchDBSource(db, opt.batch_size, de_types, data_type, dev, opt.seed, rank, world, opt.repeat, fused_degrade=bool(opt.fused_degrade))
+            src = PatchDBSource(db, opt.batch_size, de_types, data_type, dev, opt.seed, rank, world, opt.repeat, fused_degrade=bool(opt.fused_degrade), cassi=cassi)
         steps_per_epoch = src.steps_per_epoch()
     for epoch in range(start_epoch, opt.epochs):
         lr = warmup_cosine_lr(epoch, opt.lr, opt.epochs)
