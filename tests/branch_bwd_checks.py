@@ -5,7 +5,8 @@ MPHSIR_BRANCH_BWD_FUSED), shared by the CPU-emulator tests (tests/test_branch_bw
 import torch
 
 import kernel_checks as K
-from kernel_checks import GTOL, TOL, _ROUNDED, _use, rel_l2, rnd
+from guard import guarded
+from kernel_checks import GTOL, TOL, _ROUNDED, _use, inp, rel_l2, rnd
 from oracle import mp_hsir_oracle as O
 
 PROLOGUE_CASES = [(64, 2), (128, 4), (128, 2), (256, 8)]
@@ -49,14 +50,15 @@ def _prologue_inputs(dtype, C, heads, shape):
     B, H, W = shape
     M = B * H * W
     t = dict(x=rnd((B, H, W, C), 71, dtype), dmu=rnd((M // 64, C), 73),
-             lnw=1 + 0.1 * rnd((C,), 74), lnb=0.1 * rnd((C,), 75),
-             wqkv=rnd((3 * C, C), 76, dtype, scale=C ** -0.5), bqkv=0.1 * rnd((3 * C,), 77),
-             rpb=0.2 * rnd((225, heads), 78), wprojT=rnd((C, C), 79, dtype, scale=C ** -0.5),
+             lnw=rnd((C,), 74, scale=0.1, shift=1), lnb=rnd((C,), 75, scale=0.1),
+             wqkv=rnd((3 * C, C), 76, dtype, scale=C ** -0.5), bqkv=rnd((3 * C,), 77, scale=0.1),
+             rpb=rnd((225, heads), 78, scale=0.2), wprojT=rnd((C, C), 79, dtype, scale=C ** -0.5),
              dt3=rnd((M, 3 * C), 81, dtype), wsT=rnd((C, 3 * C), 82, dtype, scale=(3 * C) ** -0.5),
              d_out=rnd((B, H, W, C), 83, dtype), sa=rnd((B, H, W, C), 84, dtype), gate=rnd((M // 64, C), 85))
     return t
 
 
+@guarded
 def check_dsa_prologue(dev, dtype, C, heads, shift, shape=(2, 16, 16)):
     """win_attn_bwd with dT3 / WsT / dOut / gate: dSAt against the fp64 definition
         total = dT3[pix] WsT^T + d_out[pix] * gate[win] + dmu[win] / 64
@@ -86,8 +88,8 @@ def check_dsa_prologue(dev, dtype, C, heads, shift, shape=(2, 16, 16)):
     assert e_fused < TOL[dtype], (e_fused, TOL[dtype])
     assert e_fused <= e_three, (e_fused, e_three)
     # everything behind the prologue: the plain kernel fed the same rounded total (dmu = 0 adds nothing) returns the same bits
-    same = _from_window_rows(dsat.reshape(M, C).cpu(), B, H, W, shift).contiguous().to(dsat.device)
-    ref = ops.win_attn_bwd(t["x"], same, torch.zeros_like(t["dmu"]), *tail)
+    same = inp(_from_window_rows(dsat.reshape(M, C).cpu(), B, H, W, shift).contiguous())
+    ref = ops.win_attn_bwd(t["x"], same, K.alloc(t["dmu"].shape, role="input"), *tail)
     for name, a, b in zip(("dqkv", "XNw", "dSAt", "drpb"), (dqkv, xnw, dsat, drpb), ref):
         assert torch.equal(a.cpu(), b.cpu()), (name, rel_l2(a.float(), b.double().cpu()))
     if heads == 8:
@@ -98,6 +100,7 @@ def check_dsa_prologue(dev, dtype, C, heads, shift, shape=(2, 16, 16)):
         assert all(torch.equal(a.cpu(), b.cpu()) for a, b in zip((dqkv, xnw, dsat, drpb), one))
 
 
+@guarded
 def check_dsa_fits(dev):
     """the predicate: natural widths in the 16-bit types with the switch on; everything else keeps the launches"""
     _use(dev)
@@ -131,6 +134,7 @@ def _block(dev, name, shift):
     return blk.to(dev), c
 
 
+@guarded
 def run_block(dev, dtype, name, shift, fused, B=2, hw=(16, 16)):
     """one forward + backward of the block on `dev`: {"out", "dx", parameter name: gradient} (CPU tensors) and the launch counts"""
     _use(dev)
@@ -140,8 +144,8 @@ def run_block(dev, dtype, name, shift, fused, B=2, hw=(16, 16)):
     blk, c = _block(dev, name, shift)
     x = rnd((B, H, W, c["C"]), 301, dtype).requires_grad_(True)
     cot = rnd((B, H, W, c["C"]), 302, dtype)
-    k1 = torch.tensor([1.0 / 0.9, 0.0][:B]).to(dev)
-    k2 = torch.tensor([0.0, 1.0 / 0.95][:B]).to(dev)
+    k1 = inp(torch.tensor([1.0 / 0.9, 0.0][:B]))
+    k2 = inp(torch.tensor([0.0, 1.0 / 0.95][:B]))
     ops.ACCOUNT = {}
     with branch_bwd_fused(fused):
         y = AG.pgsstb(blk, x, k1, k2)
@@ -189,6 +193,7 @@ def block_oracle(dtype, name, shift, B=2, hw=(16, 16)):
     return want
 
 
+@guarded
 def check_block(dev, dtype, name, shift):
     """every gradient of the block within GTOL of fp64 autograd with the switch on and off; behind the changed launches the fused
     error is at most the unfused error + 0.1 GTOL; the fused run launches no gemm_tok for the spectral qkv data gradient"""
@@ -210,6 +215,7 @@ def check_block(dev, dtype, name, shift):
     return errs
 
 
+@guarded
 def check_block_deterministic(dev, dtype, name, shift):
     """two runs with the switch on return the same bits"""
     first, _ = block_run_cached(dev, dtype, name, shift, True)

@@ -3,6 +3,8 @@ MI355X tests (tests/test_gpu_kernels.py): each check drives the C ABI through mp
 device `dev` and compares with the fp64 oracle on the same (dtype-rounded) weights."""
 import torch
 
+import guard
+from guard import guarded
 from oracle import mp_hsir_oracle as O
 from util import params_from_manifest, rel_l2 as _rel
 
@@ -28,9 +30,39 @@ def rel_l2(a, b):
     return _rel(torch.as_tensor(a).detach().cpu(), torch.as_tensor(b).detach().cpu())
 
 
-def rnd(shape, seed, dtype=torch.float32, scale=1.0):
+def rnd(shape, seed, dtype=torch.float32, scale=1.0, shift=0.0):
+    """a seeded input `shift + scale * N(0, 1)` on the check's device; while a guard is active (tests/guard.py) it lies between NaN bands
+    and its CPU master is kept for the bitwise comparison after the check.  Scale and shift are applied here, not by arithmetic on the
+    result, so that LayerNorm weights, biases and tables are guarded too"""
     g = torch.Generator().manual_seed(seed)
-    return (torch.randn(shape, generator=g) * scale).to(dtype).to(_DEV[0])
+    t = torch.randn(shape, generator=g) * scale
+    if shift:
+        t = shift + t
+    return inp(t.to(dtype), seed)
+
+
+def inp(t, seed=None):
+    """a CPU tensor the check built itself (DropPath factors, index tables, fixture parameters) as a guarded input on the check's device"""
+    G = guard.active()
+    if G is not None and G.device.type == torch.device(_DEV[0]).type:
+        return G.input(t.detach(), seed)
+    return t.to(_DEV[0])
+
+
+as_input = inp          # for a check that has a local of that name
+
+
+def alloc(shape, dtype=torch.float32, device=None, fill=0, role="output"):
+    """a buffer the check itself hands to a kernel (an `out=` target, a padded weight, a partly filled operand): through the active
+    guard like everything ops.py allocates.  fill=None: torch.empty (prefilled "never written" under the guard); role "input": a
+    buffer the check fills and a kernel only reads (NaN bands)"""
+    device = torch.device(device if device is not None else _DEV[0])
+    G = guard.active()
+    if G is not None and G.device.type == device.type:
+        return G.alloc(shape, dtype, device, role, fill=fill)
+    if fill is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    return torch.full(shape, fill, dtype=dtype, device=device)
 
 
 def _use(dev):
@@ -53,6 +85,7 @@ class tok_form:
         return False
 
 
+@guarded
 def check_gemm_tok_ring(dev, dtype, M, N, K, epi, per_sample=0, ldx=None, ldy=None):
     """the ring form of the token GEMM (persistent workgroups, loader wave + LDS-DMA ring) against the workgroup-per-tile form
     (bitwise: same products, same accumulation order per output) and the fp64 product: plain / residual / branch-sum epilogues,
@@ -68,10 +101,10 @@ def check_gemm_tok_ring(dev, dtype, M, N, K, epi, per_sample=0, ldx=None, ldy=No
     H = W_ = 16
     sa = rnd((M, N), 15, dtype) if epi == 2 else None
     gate = rnd((M // 64, N), 16) if epi == 2 else None
-    keep = (1.0 + 0.25 * rnd((M // (H * W_),), 17)) if epi == 2 else None
+    keep = (rnd((M // (H * W_),), 17, scale=0.25, shift=1.0)) if epi == 2 else None
     outs = []
     for form in (1, 2):
-        yw = torch.zeros((M, ldy), dtype=dtype, device=x.device)
+        yw = alloc((M, ldy), dtype)
         with tok_form(form):
             ops.gemm_tok(x, w, bias=bias, epi=epi, res=res, sa=sa, gate=gate, keep=keep, geom=(H, W_, 4) if epi == 2 else None, out=yw[:, :N])
         outs.append(yw)
@@ -86,12 +119,13 @@ def check_gemm_tok_ring(dev, dtype, M, N, K, epi, per_sample=0, ldx=None, ldy=No
             assert float(outs[1][:, N:].abs().max()) == 0.0
 
 
+@guarded
 def check_gemm_tok(dev, dtype, M, N, K, ln, epi):
     _use(dev)
     from mp_hsir_amd import ops
     x, w = rnd((M, K), 1, dtype), rnd((N, K), 2, dtype, K ** -0.5)
     bias = rnd((N,), 3)
-    lnw, lnb = 1 + 0.1 * rnd((K,), 4), 0.1 * rnd((K,), 5)
+    lnw, lnb = rnd((K,), 4, scale=0.1, shift=1), rnd((K,), 5, scale=0.1)
     res = rnd((M, N), 6, dtype)
     y = ops.gemm_tok(x, w, bias=bias, ln=(lnw, lnb) if ln else None, epi=epi, res=res if epi else None)
     xd = x.double().cpu()
@@ -103,6 +137,7 @@ def check_gemm_tok(dev, dtype, M, N, K, ln, epi):
     assert rel_l2(y, ref) < TOL[dtype]
 
 
+@guarded
 def check_gemm_tok_per_sample_combine(dev, dtype):
     """epi 2 with a per-sample weight: the folded channel attention + PGSSTB branch sum."""
     _use(dev)
@@ -112,7 +147,7 @@ def check_gemm_tok_per_sample_combine(dev, dtype):
     v, Wb = rnd((M, C), 1, dtype), rnd((B, C, C), 2, dtype, C ** -0.5)
     res, sa = rnd((M, C), 3, dtype), rnd((M, C), 4, dtype)
     gate = rnd((B * (H // 8) * (W // 8), C), 5)
-    keep = torch.tensor([1.25, 0.0]).to(dev)
+    keep = inp(torch.tensor([1.25, 0.0]))
     y = ops.gemm_tok(v, Wb, epi=2, res=res, sa=sa, gate=gate, keep=keep, geom=(H, W, shift))
     acc = torch.einsum("bnk,bck->bnc", v.double().cpu().reshape(B, H * W, C), Wb.double().cpu()).reshape(B, H, W, C)
     # gate lives in the shifted window frame: expand to windows, un-window, roll back
@@ -122,15 +157,16 @@ def check_gemm_tok_per_sample_combine(dev, dtype):
     assert rel_l2(y.reshape(B, H, W, C), ref) < TOL[dtype]
 
 
+@guarded
 def check_gated_mlp(dev, dtype, C, hid, tpw=0, M=128, hsplit=None, res=False):
     _use(dev)
     from mp_hsir_amd import ops
     x = rnd((M, C), 1, dtype)
     r2 = rnd((M, C + 8), 8, dtype)[:, :C] if res else None          # second residual (BaseBlock skip), a strided view
-    P = {"fc1.weight": rnd((2 * hid, C), 2, scale=C ** -0.5), "fc1.bias": 0.1 * rnd((2 * hid,), 3),
-         "fc2.weight": rnd((C, hid), 4, scale=hid ** -0.5), "fc2.bias": 0.1 * rnd((C,), 5)}
-    lnw, lnb = 1 + 0.1 * rnd((C,), 6), 0.1 * rnd((C,), 7)
-    keep = torch.tensor([1.0, 1.5]).to(dev)
+    P = {"fc1.weight": rnd((2 * hid, C), 2, scale=C ** -0.5), "fc1.bias": rnd((2 * hid,), 3, scale=0.1),
+         "fc2.weight": rnd((C, hid), 4, scale=hid ** -0.5), "fc2.bias": rnd((C,), 5, scale=0.1)}
+    lnw, lnb = rnd((C,), 6, scale=0.1, shift=1), rnd((C,), 7, scale=0.1)
+    keep = inp(torch.tensor([1.0, 1.5]))
     W1, b1, W2 = ops.pack_gated_mlp(P["fc1.weight"], P["fc1.bias"], P["fc2.weight"], dtype)
     y = ops.gated_mlp_fwd(x, lnw, lnb, W1, b1, W2, P["fc2.bias"], keep=keep, rows_per_batch=M // 2, tiles_per_wave=tpw, hsplit=hsplit, res=r2)
     Pd = {k: (v.to(dtype) if k.endswith("weight") else v).double().cpu() for k, v in P.items()}
@@ -144,6 +180,7 @@ def check_gated_mlp(dev, dtype, C, hid, tpw=0, M=128, hsplit=None, res=False):
     assert rel_l2(y, ref) < TOL[dtype]
 
 
+@guarded
 def check_gated_mlp_branch_sum(dev, dtype, C, hid, B=2, H=8, W=16, shift=0, keep=True, want_y=True, res=False):
     """mphsir_gated_mlp_fwd with PV (the block's branch sum formed inside the launch) against the two launches it replaces
     (gemm_tok epi 2, then the plain gated MLP in the same kernel form): the same arithmetic in the same order -> bitwise equal."""
@@ -155,12 +192,12 @@ def check_gated_mlp_branch_sum(dev, dtype, C, hid, B=2, H=8, W=16, shift=0, keep
     sa = rnd((M, C), 12, dtype)
     Mb = rnd((B, C, C), 13, scale=C ** -0.5).to(dtype)
     gate = rnd((B * (H * W // 64), C), 14)
-    k1 = torch.tensor(([1.0, 1.25, 0.0, 1.5] * B)[:B]).to(dev) if keep else None
-    k2 = torch.tensor(([1.5, 1.0, 1.25, 0.0] * B)[:B]).to(dev) if keep else None
+    k1 = inp(torch.tensor(([1.0, 1.25, 0.0, 1.5] * B)[:B])) if keep else None
+    k2 = inp(torch.tensor(([1.5, 1.0, 1.25, 0.0] * B)[:B])) if keep else None
     r2 = rnd((M, C + 8), 8, dtype)[:, :C] if res else None
-    fc1w, fc1b = rnd((2 * hid, C), 2, scale=C ** -0.5), 0.1 * rnd((2 * hid,), 3)
-    fc2w, fc2b = rnd((C, hid), 4, scale=hid ** -0.5), 0.1 * rnd((C,), 5)
-    lnw, lnb = 1 + 0.1 * rnd((C,), 6), 0.1 * rnd((C,), 7)
+    fc1w, fc1b = rnd((2 * hid, C), 2, scale=C ** -0.5), rnd((2 * hid,), 3, scale=0.1)
+    fc2w, fc2b = rnd((C, hid), 4, scale=hid ** -0.5), rnd((C,), 5, scale=0.1)
+    lnw, lnb = rnd((C,), 6, scale=0.1, shift=1), rnd((C,), 7, scale=0.1)
     W1, b1, W2 = ops.pack_gated_mlp(fc1w, fc1b, fc2w, dtype)
     y0 = ops.gemm_tok(v, Mb, epi=2, res=x, sa=sa, gate=gate, keep=k1, geom=(H, W, shift))
     z0 = ops.gated_mlp_fwd(y0, lnw, lnb, W1, b1, W2, fc2b, keep=k2, rows_per_batch=H * W, tiles_per_wave=3, res=r2)
@@ -179,13 +216,14 @@ def check_gated_mlp_branch_sum(dev, dtype, C, hid, B=2, H=8, W=16, shift=0, keep
 TWIN = {torch.bfloat16: 4e-3, torch.float16: 5e-4}      # measured: 1.1e-3 ... 2.6e-3 / 1.4e-4 ... 3.2e-4
 
 
+@guarded
 def check_gated_mlp_fp32_twin(dev, dtype, C=128, hid=340, M=1024, tpw=3, hsplit=None):
     _use(dev)
     from mp_hsir_amd import ops
     x = rnd((M, C), 1, dtype)
-    fc1w, fc1b = rnd((2 * hid, C), 2, scale=C ** -0.5), 0.1 * rnd((2 * hid,), 3)
-    fc2w, fc2b = rnd((C, hid), 4, scale=hid ** -0.5), 0.1 * rnd((C,), 5)
-    lnw, lnb = 1 + 0.1 * rnd((C,), 6), 0.1 * rnd((C,), 7)
+    fc1w, fc1b = rnd((2 * hid, C), 2, scale=C ** -0.5), rnd((2 * hid,), 3, scale=0.1)
+    fc2w, fc2b = rnd((C, hid), 4, scale=hid ** -0.5), rnd((C,), 5, scale=0.1)
+    lnw, lnb = rnd((C,), 6, scale=0.1, shift=1), rnd((C,), 7, scale=0.1)
     W1, b1, W2 = ops.pack_gated_mlp(fc1w, fc1b, fc2w, dtype)
     y = ops.gated_mlp_fwd(x, lnw, lnb, W1, b1, W2, fc2b, tiles_per_wave=tpw, hsplit=hsplit)
     W1f, b1f, W2f = ops.pack_gated_mlp(fc1w.to(dtype).float(), fc1b, fc2w.to(dtype).float(), torch.float32)
@@ -195,6 +233,7 @@ def check_gated_mlp_fp32_twin(dev, dtype, C=128, hid=340, M=1024, tpw=3, hsplit=
     return e
 
 
+@guarded
 def check_pass_a_rows_fp32_twin(dev, dtype, C=64, heads=2, shape=(1, 32, 64), row_segments=2):
     """the row-walking fused pass A (16-bit only) against gemm_tok -> dwconv_gram in fp32 on the rounded inputs: v and the summed
     Gram / norm partials"""
@@ -214,6 +253,7 @@ def check_pass_a_rows_fp32_twin(dev, dtype, C=64, heads=2, shape=(1, 32, 64), ro
     return ev, eg, es
 
 
+@guarded
 def check_gdfn_fused_fp32_twin(dev, dtype, D=64, hid=170, shape=(1, 16, 32)):
     """the fused GDFN (16-bit only) against the three-launch chain in fp32 on the rounded inputs and weights"""
     _use(dev)
@@ -223,13 +263,13 @@ def check_gdfn_fused_fp32_twin(dev, dtype, D=64, hid=170, shape=(1, 16, 32)):
     assert ops.gdfn_fused_fits(D, HP, H, W, dtype)
     x = rnd((B, H, W, D), 41, dtype)
     wi, wd, wo = rnd((2 * hid, D), 42, scale=D ** -0.5), rnd((2 * hid, 1, 3, 3), 43, scale=1 / 3), rnd((D, hid), 44, scale=hid ** -0.5)
-    lnw, lnb = 1 + 0.1 * rnd((D,), 45), 0.1 * rnd((D,), 46)
-    w_in = torch.zeros((2 * HP, D), dtype=dtype, device=dev)
+    lnw, lnb = rnd((D,), 45, scale=0.1, shift=1), rnd((D,), 46, scale=0.1)
+    w_in = alloc((2 * HP, D), dtype, role="input")
     w_in[:hid], w_in[HP:HP + hid] = wi[:hid].to(dtype), wi[hid:].to(dtype)
-    w9 = torch.zeros((9, 2 * HP), device=dev)
+    w9 = alloc((9, 2 * HP), role="input")
     w9s = ops.pack_dw(wd)
     w9[:, :hid], w9[:, HP:HP + hid] = w9s[:, :hid], w9s[:, hid:]
-    w_out = torch.zeros((D, HP), dtype=dtype, device=dev)
+    w_out = alloc((D, HP), dtype, role="input")
     w_out[:, :hid] = wo.to(dtype)
     x2 = x.reshape(-1, D)
     y = ops.gdfn_fused(x2, (lnw, lnb), w_in, w9, w_out, B, H, W)
@@ -241,9 +281,10 @@ def check_gdfn_fused_fp32_twin(dev, dtype, D=64, hid=170, shape=(1, 16, 32)):
 
 
 def _block_params(manifest_entry, prefix):
-    return {k: v.to(_DEV[0]) for k, v in params_from_manifest(manifest_entry, prefix, dtype=torch.float32).items()}
+    return {k: inp(v) for k, v in params_from_manifest(manifest_entry, prefix, dtype=torch.float32).items()}
 
 
+@guarded
 def check_win_attn(dev, dtype, man, prefix, heads, shift, shape, manifest):
     _use(dev)
     from mp_hsir_amd import ops
@@ -273,6 +314,7 @@ def check_win_attn(dev, dtype, man, prefix, heads, shift, shape, manifest):
     assert rel_l2(gate, g_ref) < TOL[dtype] * (4 if dtype != torch.float32 else 1)
 
 
+@guarded
 def check_spectral_attention_chain(dev, dtype, C, heads, shape, nsplit):
     """gemm_tok (1x1 qkv) -> dwconv_gram -> spectral_fold -> gemm_tok (per-sample M) == oracle spectral_attention"""
     _use(dev)
@@ -280,7 +322,7 @@ def check_spectral_attention_chain(dev, dtype, C, heads, shape, nsplit):
     B, H, W = shape
     x = rnd((B, H, W, C), 21, dtype)
     P = {"qkv.weight": rnd((3 * C, C, 1, 1), 22, scale=C ** -0.5), "qkv_dwconv.weight": rnd((3 * C, 1, 3, 3), 23, scale=1 / 3),
-         "project_out.weight": rnd((C, C, 1, 1), 24, scale=C ** -0.5), "temperature": 1 + 0.3 * rnd((heads, 1, 1), 25)}
+         "project_out.weight": rnd((C, C, 1, 1), 24, scale=C ** -0.5), "temperature": rnd((heads, 1, 1), 25, scale=0.3, shift=1)}
     wqkv = P["qkv.weight"].reshape(3 * C, C).to(dtype)
     t = ops.gemm_tok(x.reshape(-1, C), wqkv)
     w9 = ops.pack_dw(P["qkv_dwconv.weight"])
@@ -324,6 +366,7 @@ ROWS_CASES_GPU = [(64, 2, (2, 64, 64), 4, False), (128, 4, (2, 32, 32), 2, False
                   (256, 8, (1, 128, 128), 8, False), (256, 8, (2, 32, 32), 2, False), (256, 8, (1, 64, 64), 4, True)]
 
 
+@guarded
 def check_fused_pass_a(dev, dtype, C, heads, shape, nsplit, ln, hgroups=None, row_segments=0):
     """qkv_dwconv_gram (LN + 1x1 qkv + depthwise 3x3 + Gram / norms in one launch) == gemm_tok -> dwconv_gram, and the
     chain through spectral_fold / pass B == oracle spectral_attention (ref :96-114; with ln: norm1 of :476 first)."""
@@ -337,8 +380,8 @@ def check_fused_pass_a(dev, dtype, C, heads, shape, nsplit, ln, hgroups=None, ro
         assert ops.qkv_dwconv_gram_fits(C, heads, H, W, dtype)
     x = rnd((B, H, W, C), 61, dtype)
     P = {"qkv.weight": rnd((3 * C, C, 1, 1), 62, scale=C ** -0.5), "qkv_dwconv.weight": rnd((3 * C, 1, 3, 3), 63, scale=1 / 3),
-         "project_out.weight": rnd((C, C, 1, 1), 64, scale=C ** -0.5), "temperature": 1 + 0.3 * rnd((heads, 1, 1), 65)}
-    lnp = (1 + 0.2 * rnd((C,), 66), 0.1 * rnd((C,), 67)) if ln else None
+         "project_out.weight": rnd((C, C, 1, 1), 64, scale=C ** -0.5), "temperature": rnd((heads, 1, 1), 65, scale=0.3, shift=1)}
+    lnp = (rnd((C,), 66, scale=0.2, shift=1), rnd((C,), 67, scale=0.1)) if ln else None
     wqkv = P["qkv.weight"].reshape(3 * C, C).to(dtype).contiguous()
     w9 = ops.pack_dw(P["qkv_dwconv.weight"])
     x2 = x.reshape(-1, C)
@@ -371,6 +414,7 @@ def check_fused_pass_a(dev, dtype, C, heads, shape, nsplit, ln, hgroups=None, ro
     assert rel_l2(y.reshape(B, H, W, C), ref) < tol * (2 if dtype != torch.float32 else 1)
 
 
+@guarded
 def check_gdfn_chain(dev, dtype):
     """gemm_tok(LN + project_in) -> dwconv_gate -> gemm_tok(project_out + residual) == x + gdfn(LN(x))"""
     _use(dev)
@@ -380,13 +424,13 @@ def check_gdfn_chain(dev, dtype):
     x = rnd((B, H, W, C), 31, dtype)
     P = {"project_in.weight": rnd((2 * hid, C, 1, 1), 32, scale=C ** -0.5), "dwconv.weight": rnd((2 * hid, 1, 3, 3), 33, scale=1 / 3),
          "project_out.weight": rnd((C, hid, 1, 1), 34, scale=hid ** -0.5)}
-    lnw, lnb = 1 + 0.1 * rnd((C,), 35), 0.1 * rnd((C,), 36)
-    w_in = torch.zeros((2 * HP, C), dtype=dtype, device=dev)
+    lnw, lnb = rnd((C,), 35, scale=0.1, shift=1), rnd((C,), 36, scale=0.1)
+    w_in = alloc((2 * HP, C), dtype, role="input")
     w_in[:hid], w_in[HP:HP + hid] = P["project_in.weight"].reshape(2 * hid, C)[:hid].to(dtype), P["project_in.weight"].reshape(2 * hid, C)[hid:].to(dtype)
-    w9 = torch.zeros((9, 2 * HP), device=dev)
+    w9 = alloc((9, 2 * HP), role="input")
     w9s = ops.pack_dw(P["dwconv.weight"])
     w9[:, :hid], w9[:, HP:HP + hid] = w9s[:, :hid], w9s[:, hid:]
-    w_out = torch.zeros((C, HP), dtype=dtype, device=dev)
+    w_out = alloc((C, HP), dtype, role="input")
     w_out[:, :hid] = P["project_out.weight"].reshape(C, hid).to(dtype)
     x2 = x.reshape(-1, C)
     t = ops.gemm_tok(x2, w_in, ln=(lnw, lnb))
@@ -403,6 +447,7 @@ GDFN_FUSED_CASES = [(64, 170, (1, 8, 16), None), (64, 170, (2, 16, 32), 2), (128
 GDFN_FUSED_CASES_GPU = [(128, 340, (1, 64, 64), None), (256, 680, (2, 32, 32), None), (192, 510, (1, 32, 48), None), (64, 170, (2, 64, 64), None)]
 
 
+@guarded
 def check_gdfn_fused(dev, dtype, D, hid, shape, nsplit):
     """mphsir_gdfn_fused == x + gdfn(LN(x)) (oracle, fp64) and == the three-launch chain gemm_tok -> dwconv_gate -> gemm_tok
     (which rounds t to the storage type between the 1x1 and the depthwise conv; the fused kernel keeps it in fp32)."""
@@ -414,14 +459,14 @@ def check_gdfn_fused(dev, dtype, D, hid, shape, nsplit):
     x = rnd((B, H, W, D), 41, dtype)
     P = {"project_in.weight": rnd((2 * hid, D, 1, 1), 42, scale=D ** -0.5), "dwconv.weight": rnd((2 * hid, 1, 3, 3), 43, scale=1 / 3),
          "project_out.weight": rnd((D, hid, 1, 1), 44, scale=hid ** -0.5)}
-    lnw, lnb = 1 + 0.1 * rnd((D,), 45), 0.1 * rnd((D,), 46)
-    w_in = torch.zeros((2 * HP, D), dtype=dtype, device=dev)
+    lnw, lnb = rnd((D,), 45, scale=0.1, shift=1), rnd((D,), 46, scale=0.1)
+    w_in = alloc((2 * HP, D), dtype, role="input")
     wi = P["project_in.weight"].reshape(2 * hid, D)
     w_in[:hid], w_in[HP:HP + hid] = wi[:hid].to(dtype), wi[hid:].to(dtype)
-    w9 = torch.zeros((9, 2 * HP), device=dev)
+    w9 = alloc((9, 2 * HP), role="input")
     w9s = ops.pack_dw(P["dwconv.weight"])
     w9[:, :hid], w9[:, HP:HP + hid] = w9s[:, :hid], w9s[:, hid:]
-    w_out = torch.zeros((D, HP), dtype=dtype, device=dev)
+    w_out = alloc((D, HP), dtype, role="input")
     w_out[:, :hid] = P["project_out.weight"].reshape(D, hid).to(dtype)
     x2 = x.reshape(-1, D)
     y = ops.gdfn_fused(x2, (lnw, lnb), w_in, w9, w_out, B, H, W, nsplit=nsplit)
@@ -442,6 +487,7 @@ def check_gdfn_fused(dev, dtype, D, hid, shape, nsplit):
     assert float((tk.float() - t.float()).abs().max()) <= float(t.float().abs().max()) * 2.0 ** -7
 
 
+@guarded
 def check_dwconv_gate_bwd(dev, dtype, shape=(2, 16, 32), hid=85):
     """dwconv_gate_bwd (depthwise conv recomputed inside the gate backward) vs fp64 autograd of u = gelu(dw(t)[:hid]) * dw(t)[hid:],
     and vs the two launches dwconv3x3 -> gdfn_gate_bwd (which round the conv output to the storage type in between)."""
@@ -451,13 +497,13 @@ def check_dwconv_gate_bwd(dev, dtype, shape=(2, 16, 32), hid=85):
     B, H, W = shape
     HP = ops.round_up(hid, 32)
     M = B * H * W
-    t = torch.zeros((M, 2 * HP), dtype=dtype, device=dev)
+    t = alloc((M, 2 * HP), dtype, role="input")
     tv = rnd((M, 2 * hid), 81, dtype)
     t[:, :hid], t[:, HP:HP + hid] = tv[:, :hid], tv[:, hid:]
-    du = torch.zeros((M, HP), dtype=dtype, device=dev)
+    du = alloc((M, HP), dtype, role="input")
     du[:, :hid] = rnd((M, hid), 82, dtype)
     w = rnd((2 * hid, 1, 3, 3), 83, scale=1 / 3)
-    w9 = torch.zeros((9, 2 * HP), device=dev)
+    w9 = alloc((9, 2 * HP), role="input")
     w9s = ops.pack_dw(w)
     w9[:, :hid], w9[:, HP:HP + hid] = w9s[:, :hid], w9s[:, hid:]
     u, dtd = ops.dwconv_gate_bwd(t, w9, du, B, H, W)
@@ -473,6 +519,7 @@ def check_dwconv_gate_bwd(dev, dtype, shape=(2, 16, 32), hid=85):
     assert float(dtd[:, hid:HP].abs().max()) == 0.0 and float(dtd[:, HP + hid:].abs().max()) == 0.0      # padded channels stay zero
 
 
+@guarded
 def check_dwconv_plain(dev, dtype, shape):
     """forward, backward-data (flipped taps) and weight gradient of the depthwise 3x3 vs torch autograd (fp64)."""
     _use(dev)
@@ -498,6 +545,7 @@ DW_BWD_CASES = [(1, 8, 16, 32), (2, 16, 32, 96), (1, 24, 16, 128), (2, 8, 32, 35
 DW_BWD_CASES_GPU = [(32, 64, 64, 384), (4, 64, 64, 704), (2, 128, 128, 192)]
 
 
+@guarded
 def check_dwconv_bwd(dev, dtype, shape):
     """mphsir_dwconv3x3_bwd (dX and dW of one depthwise conv in one launch) vs the two launches (dX bitwise: the same tap order)
     and vs torch autograd in fp64; the parameter-layout output (col_ranges) as well."""
@@ -528,16 +576,17 @@ def check_dwconv_bwd(dev, dtype, shape):
     assert torch.equal(dx2, dx2r) and torch.equal(dw2, dw2r)
 
 
-def check_gated_mlp_bwd(dev, dtype, C, hid, variant=0, hsplit=None):
-    """HIP data-gradient kernel + token-reduction GEMMs vs autograd of the fp64 oracle."""
+@guarded
+def check_gated_mlp_bwd(dev, dtype, C, hid, variant=0, hsplit=None, M=128):
+    """HIP data-gradient kernel + token-reduction GEMMs vs autograd of the fp64 oracle; M tokens = M // 64 samples of 64 rows, each with
+    its own DropPath factor."""
     _use(dev)
     from mp_hsir_amd import ops
-    M = 128
     x, dy = rnd((M, C), 1, dtype), rnd((M, C), 9, dtype)
-    P = {"fc1.weight": rnd((2 * hid, C), 2, scale=C ** -0.5), "fc1.bias": 0.1 * rnd((2 * hid,), 3),
-         "fc2.weight": rnd((C, hid), 4, scale=hid ** -0.5), "fc2.bias": 0.1 * rnd((C,), 5)}
-    lnw, lnb = 1 + 0.1 * rnd((C,), 6), 0.1 * rnd((C,), 7)
-    keep = torch.tensor([1.0, 1.5]).to(dev)
+    P = {"fc1.weight": rnd((2 * hid, C), 2, scale=C ** -0.5), "fc1.bias": rnd((2 * hid,), 3, scale=0.1),
+         "fc2.weight": rnd((C, hid), 4, scale=hid ** -0.5), "fc2.bias": rnd((C,), 5, scale=0.1)}
+    lnw, lnb = rnd((C,), 6, scale=0.1, shift=1), rnd((C,), 7, scale=0.1)
+    keep = inp(torch.tensor(([1.0, 1.5] * (M // 64))[:M // 64]))
     W1, b1, W2 = ops.pack_gated_mlp(P["fc1.weight"], P["fc1.bias"], P["fc2.weight"], dtype)
     HP = W2.shape[1]
     dm = (dy.float() * keep.repeat_interleave(64)[:, None]).to(dtype)
@@ -566,6 +615,7 @@ def check_gated_mlp_bwd(dev, dtype, C, hid, variant=0, hsplit=None):
     assert rel_l2(dln[0], lw.grad) < tol and rel_l2(dln[1], lb.grad) < tol
 
 
+@guarded
 def check_gated_mlp_wgrad(dev, dtype, C, hid, M=256, nch=1, ranges=8, keep=True):
     """mphsir_gated_mlp_wgrad (parameter gradients by recomputation, fp32 accumulators per hidden slab and token range) against
     (a) autograd of the fp64 oracle and (b) the token-reduction GEMMs of the operands the data-gradient kernel writes (the path
@@ -574,11 +624,11 @@ def check_gated_mlp_wgrad(dev, dtype, C, hid, M=256, nch=1, ranges=8, keep=True)
     _use(dev)
     from mp_hsir_amd import ops
     x, dy = rnd((M, C), 1, dtype), rnd((M, C), 9, dtype)
-    P = {"fc1.weight": rnd((2 * hid, C), 2, scale=C ** -0.5), "fc1.bias": 0.1 * rnd((2 * hid,), 3),
-         "fc2.weight": rnd((C, hid), 4, scale=hid ** -0.5), "fc2.bias": 0.1 * rnd((C,), 5)}
-    lnw, lnb = 1 + 0.1 * rnd((C,), 6), 0.1 * rnd((C,), 7)
+    P = {"fc1.weight": rnd((2 * hid, C), 2, scale=C ** -0.5), "fc1.bias": rnd((2 * hid,), 3, scale=0.1),
+         "fc2.weight": rnd((C, hid), 4, scale=hid ** -0.5), "fc2.bias": rnd((C,), 5, scale=0.1)}
+    lnw, lnb = rnd((C,), 6, scale=0.1, shift=1), rnd((C,), 7, scale=0.1)
     nb = M // 64
-    kf = (1.0 + 0.25 * torch.arange(nb) / nb).float().to(dev) if keep else None
+    kf = inp((1.0 + 0.25 * torch.arange(nb) / nb).float()) if keep else None
     W1, b1, W2 = ops.pack_gated_mlp(P["fc1.weight"], P["fc1.bias"], P["fc2.weight"], dtype)
     W1T, W2T = W1.t().contiguous(), W2.t().contiguous()
     HP = W2.shape[1]
@@ -617,6 +667,7 @@ def check_gated_mlp_wgrad(dev, dtype, C, hid, M=256, nch=1, ranges=8, keep=True)
     assert rel_l2(db1, Pd["fc1.bias"].grad) < tol and rel_l2(db2, Pd["fc2.bias"].grad) < tol
 
 
+@guarded
 def check_l1_clamp_loss(dev):
     """mphsir_l1_clamp_loss (loss + gradient in one pass) vs the oracle's clamp + L1 and torch autograd through it (train.py:58-61),
     incl. values exactly on the clamp bounds / equal to the target, a length that is not a multiple of 4, and an upstream factor."""
@@ -655,6 +706,7 @@ def check_l1_clamp_loss(dev):
         assert torch.isfinite(y.grad).all() and float(y.grad.view(-1)[5]) == 0.0 and rel_l2(y.grad, yr.grad) < 1e-6
 
 
+@guarded
 def check_multi_copy(dev):
     """mphsir_multi_copy: many fp32 tensors -> their arena slots in one launch: lengths around the 4096-float block, a source that
     is not 16-byte aligned, repeated use of the table ring."""
@@ -662,7 +714,7 @@ def check_multi_copy(dev):
     from mp_hsir_amd import ops
     d = torch.device(dev)
     lens = (5, 4096, 4097, 12, 100000, 3, 8192, 1)
-    arena = torch.zeros(sum((n + 3) // 4 * 4 for n in lens) + 8, device=d)
+    arena = alloc((sum((n + 3) // 4 * 4 for n in lens) + 8,))
     dsts, o = [], 0
     for n in lens:
         dsts.append(arena[o:o + n])
@@ -692,6 +744,7 @@ class tn_form:
         return False
 
 
+@guarded
 def check_gemm_tn(dev, dtype, M, N1, N2, nsplit, batch, tile128=None):
     _use(dev)
     from mp_hsir_amd import ops
@@ -709,6 +762,7 @@ def check_gemm_tn(dev, dtype, M, N1, N2, nsplit, batch, tile128=None):
         assert rel_l2(c2, wide[:, 8:8 + N1].double().cpu().t() @ b.double().cpu()) < (3e-6 if dtype == torch.float32 else 1e-2)
 
 
+@guarded
 def check_conv3x3(dev, dtype, B, H, W, Cin, Cout):
     """implicit-GEMM dense conv: forward, input gradient (flipped/transposed weights) and weight gradient
     (im2col + token-reduction GEMM) vs torch autograd in fp64."""
@@ -746,6 +800,7 @@ def check_conv3x3(dev, dtype, B, H, W, Cin, Cout):
         assert dw4.is_contiguous() and torch.equal(dw4.cpu(), dw2.cpu()) and torch.equal(dw5.cpu(), dw2.cpu())
 
 
+@guarded
 def check_reduce_parts(dev):
     """mphsir_reduce_parts: deferred scope (several segments, one launch), odd lengths (scalar path), batched layout,
     > 32 segments (two launches), and bitwise equality with an ordered fp32 sum."""
@@ -769,17 +824,19 @@ def check_reduce_parts(dev):
     assert torch.equal(ops.reduce_parts(big).cpu(), ops.reduce_parts(big.clone()).cpu())   # fixed order: bitwise reproducible
 
 
+@guarded
 def check_pack_gather(dev, dtype):
     _use(dev)
     from mp_hsir_amd import ops
     arena = rnd((1000,), 95)
     g = torch.Generator().manual_seed(5)
-    idx = torch.randint(-1, 1000, (256,), generator=g, dtype=torch.int32).to(arena.device)
+    idx = inp(torch.randint(-1, 1000, (256,), generator=g, dtype=torch.int32))
     out = ops.pack_gather(arena, idx, dtype)
     ref = torch.where(idx >= 0, arena[idx.clamp(min=0).long()], torch.zeros(())).to(dtype)
     assert torch.equal(out.cpu(), ref.cpu())
 
 
+@guarded
 def check_reduce_block(dev):
     """2-D segments of mphsir_reduce_parts: sub-block extraction with un-padding, stacking two row ranges into one
     output, a transposed destination, a single-row block and an unaligned sub-block (scalar path)."""
@@ -788,21 +845,25 @@ def check_reduce_block(dev):
     part = rnd((5, 24, 40), 120)
     full = part.double().sum(0)
     with ops.reduce_scope():
-        a = torch.empty((12, 40), dtype=torch.float32, device=part.device)
+        a = alloc((12, 40), fill=None)
         ops.reduce_block(part, 0, 6, 0, 40, a[:6])
         ops.reduce_block(part, 16, 6, 0, 40, a[6:])
-        b = ops.reduce_block(part, 4, 8, 8, 16, torch.empty((8, 16), dtype=torch.float32, device=part.device))
-        c = ops.reduce_block(part, 0, 9, 0, 24, torch.empty((24, 9), dtype=torch.float32, device=part.device), transpose=True)
-        d = ops.reduce_block(part, 3, 1, 5, 7, torch.empty((1, 7), dtype=torch.float32, device=part.device))
-        e = ops.reduce_block(part, 2, 5, 3, 10, torch.empty((5, 10), dtype=torch.float32, device=part.device))
-        wide = torch.zeros((8, 32), dtype=torch.float32, device=part.device)
+        b = ops.reduce_block(part, 4, 8, 8, 16, alloc((8, 16), fill=None))
+        c = ops.reduce_block(part, 0, 9, 0, 24, alloc((24, 9), fill=None), transpose=True)
+        d = ops.reduce_block(part, 3, 1, 5, 7, alloc((1, 7), fill=None))
+        e = ops.reduce_block(part, 2, 5, 3, 10, alloc((5, 10), fill=None))
+        wide = alloc((8, 32))
         ops.reduce_block(part, 1, 8, 4, 12, wide[:, 8:20])
+        one = rnd((1, 1, 8), 121)                                     # one partial, one row
+        f = ops.reduce_block(one, 0, 1, 0, 8, alloc((1, 8), fill=None))
+    assert torch.equal(f.cpu(), one[0].cpu())
     assert rel_l2(a, torch.cat([full[:6], full[16:22]])) < 3e-7
     assert rel_l2(b, full[4:12, 8:24]) < 3e-7 and rel_l2(c, full[:9, :24].t()) < 3e-7
     assert rel_l2(d, full[3:4, 5:12]) < 3e-7 and rel_l2(e, full[2:7, 3:13]) < 3e-7
     assert rel_l2(wide[:, 8:20], full[1:9, 4:16]) < 3e-7 and float(wide[:, :8].abs().sum()) == 0 and float(wide[:, 20:].abs().sum()) == 0
 
 
+@guarded
 def check_gemm_tn_grouped(dev, dt=torch.bfloat16):
     """16-bit token-reduction GEMMs deferred inside a reduce_scope are issued as ONE grouped launch: mixed widths (64- and
     128-wide tile classes in one group), column sums, un-padding blocks, > 8 problems (two launches) == separate calls."""
@@ -830,6 +891,7 @@ _ROUNDED = ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.we
 GTOL = {torch.float32: 2e-5, torch.bfloat16: 6e-2, torch.float16: 2e-2}
 
 
+@guarded
 def check_pgsstb_backward_oracle(dev, dtype, name, B=2, hw=(16, 16), drop_path=True):
     """A whole PGSSTB block (win_attn_bwd + ln_bwd_win + combine_bwd + pg_gate_bwd + the channel-attention backward chain +
     gated_mlp_bwd + every token-reduction GEMM) at one shape class of BLOCK_CASES, batch 2, WITH DropPath factors, against
@@ -850,8 +912,8 @@ def check_pgsstb_backward_oracle(dev, dtype, name, B=2, hw=(16, 16), drop_path=T
     blk = blk.to(dev)
     x = rnd((B, H, W, C), 301, dtype).requires_grad_(True)
     cot = rnd((B, H, W, C), 302, dtype)
-    k1 = torch.tensor([1.0 / 0.9, 0.0][:B] if drop_path else [1.0] * B).to(dev)
-    k2 = torch.tensor([0.0, 1.0 / 0.95][:B] if drop_path else [1.0] * B).to(dev)
+    k1 = inp(torch.tensor([1.0 / 0.9, 0.0][:B] if drop_path else [1.0] * B))
+    k2 = inp(torch.tensor([0.0, 1.0 / 0.95][:B] if drop_path else [1.0] * B))
     y = AG.pgsstb(blk, x, k1, k2)
     (y.float() * cot.float()).sum().backward()
     # oracle
@@ -873,6 +935,7 @@ def check_pgsstb_backward_oracle(dev, dtype, name, B=2, hw=(16, 16), drop_path=T
     return errs
 
 
+@guarded
 def check_win_attn_bwd_head_split(dev, dtype, C=128, heads=4, shape=(2, 16, 16)):
     """win_attn_bwd with the heads of a window dealt to several workgroups returns exactly what one workgroup per window does."""
     _use(dev)
@@ -880,9 +943,9 @@ def check_win_attn_bwd_head_split(dev, dtype, C=128, heads=4, shape=(2, 16, 16))
     B, H, W = shape
     x, dsa = rnd((B, H, W, C), 71, dtype), rnd((B, H, W, C), 72, dtype)
     dmu = rnd((B * H * W // 64, C), 73)
-    lnw, lnb = 1 + 0.1 * rnd((C,), 74), 0.1 * rnd((C,), 75)
-    wqkv, bqkv = rnd((3 * C, C), 76, dtype, scale=C ** -0.5), 0.1 * rnd((3 * C,), 77)
-    rpb = 0.2 * rnd((225, heads), 78)
+    lnw, lnb = rnd((C,), 74, scale=0.1, shift=1), rnd((C,), 75, scale=0.1)
+    wqkv, bqkv = rnd((3 * C, C), 76, dtype, scale=C ** -0.5), rnd((3 * C,), 77, scale=0.1)
+    rpb = rnd((225, heads), 78, scale=0.2)
     wprojT = rnd((C, C), 79, dtype, scale=C ** -0.5)
     ref = ops.win_attn_bwd(x, dsa, dmu, lnw, lnb, wqkv, bqkv, rpb, wprojT, heads, 4, head_split=1)
     for hs in (2, heads):
@@ -892,14 +955,15 @@ def check_win_attn_bwd_head_split(dev, dtype, C=128, heads=4, shape=(2, 16, 16))
     assert all(torch.equal(a, b) for a, b in zip(auto, ref))
 
 
-def check_combine_bwd(dev, dtype, C=128, shift=4):
+@guarded
+def check_combine_bwd(dev, dtype, C=128, shift=4, shape=(2, 16, 24)):
     """mphsir_combine_bwd against its definition (backward of gemm_tok epilogue 2)."""
     _use(dev)
     from mp_hsir_amd import ops
-    B, H, W = 2, 16, 24
+    B, H, W = shape
     dy, sa = rnd((B, H, W, C), 311, dtype), rnd((B, H, W, C), 312, dtype)
     gate = rnd((B * (H // 8) * (W // 8), C), 313)
-    keep = torch.tensor([1.25, 0.5]).to(dev)
+    keep = inp(torch.tensor([1.25, 0.5][:B]))
     d_out, d_sa, dgate = ops.combine_bwd(dy, sa, gate, keep, shift)
     dyd, sad = dy.double().cpu(), sa.double().cpu()
     do_ref = (keep.double().cpu().reshape(B, 1, 1, 1) * dyd).to(dtype).double()          # stored rounded
@@ -918,6 +982,7 @@ def check_combine_bwd(dev, dtype, C=128, shift=4):
     assert d_out2.data_ptr() == dy.data_ptr() and rel_l2(d_sa2, dyd * gimg) < TOL[dtype]
 
 
+@guarded
 def check_pg_gate_bwd(dev, C, cr, nW=20, factor_dtype=torch.float32):
     """mphsir_pg_gate_bwd (+ the factor-product GEMM that yields its eight parameter gradients) against fp64 autograd
     of the oracle's pg_spectral_gate."""
@@ -928,7 +993,7 @@ def check_pg_gate_bwd(dev, C, cr, nW=20, factor_dtype=torch.float32):
     shapes = {"linear_down.weight": (r, C), "linear_up.weight": (C, r), "linear_prompt.weight": (128, C), "prompt_param": (1, 1, 128, r),
               "q.weight": (r, r), "kv.weight": (2 * r, r), "proj.weight": (r, r), "proj.bias": (r,)}
     P = {k: det_value("local_spectral_attn." + k, shp).float() for k, shp in shapes.items()}
-    pg = {k: v.to(dev).contiguous() for k, v in P.items()}
+    pg = {k: inp(v.contiguous()) for k, v in P.items()}
     pg["prompt_param"] = pg["prompt_param"].reshape(128, r).contiguous()
     mu, dgate = rnd((nW, C), 321), rnd((nW, C), 322)
     with ops.reduce_scope():
@@ -943,6 +1008,7 @@ def check_pg_gate_bwd(dev, C, cr, nW=20, factor_dtype=torch.float32):
         assert rel_l2(g[k].reshape(shapes[k]), Pd["pg." + k].grad) < tol, (k, rel_l2(g[k].reshape(shapes[k]), Pd["pg." + k].grad))
 
 
+@guarded
 def check_pg_gate_fwd(dev, C, cr, nW=20):
     """mphsir_pg_gate_fwd on its own against the oracle's pg_spectral_gate (MP_HSIR.py:136-152) -- incl. widths the shipped
     nets do not have (C = 512 with r = 16: the register-resident Wup path must not take them)."""
@@ -953,7 +1019,7 @@ def check_pg_gate_fwd(dev, C, cr, nW=20):
     shapes = {"linear_down.weight": (r, C), "linear_up.weight": (C, r), "linear_prompt.weight": (128, C), "prompt_param": (1, 1, 128, r),
               "q.weight": (r, r), "kv.weight": (2 * r, r), "proj.weight": (r, r), "proj.bias": (r,)}
     P = {k: det_value("local_spectral_attn." + k, shp).float() for k, shp in shapes.items()}
-    pg = {k: v.to(dev).contiguous() for k, v in P.items()}
+    pg = {k: inp(v.contiguous()) for k, v in P.items()}
     pg["prompt_param"] = pg["prompt_param"].reshape(128, r).contiguous()
     mu = rnd((nW, C), 323)
     gate = ops.pg_gate_fwd(mu, pg)
@@ -962,6 +1028,7 @@ def check_pg_gate_fwd(dev, C, cr, nW=20):
     assert rel_l2(gate, want) < 2e-5, rel_l2(gate, want)
 
 
+@guarded
 def check_fold_bwd_split_dm(dev, dtype, C=64, heads=2, B=2, nsp=5):
     """mphsir_spectral_fold_bwd with dM handed over as the SPLIT PARTIALS of the token-reduction GEMM (B, splits, C, C): the kernel's
     in-order sum while staging against the ordered-sum launch (reduce_parts) followed by the plain call"""
@@ -970,7 +1037,7 @@ def check_fold_bwd_split_dm(dev, dtype, C=64, heads=2, B=2, nsp=5):
     hd = C // heads
     gp = rnd((B, 1, heads, hd, hd), 601)
     sp = rnd((B, 1, 2, C), 602).abs() + 0.5
-    temp = (1 + 0.3 * rnd((heads,), 603)).contiguous()
+    temp = (rnd((heads,), 603, scale=0.3, shift=1)).contiguous()
     wo = rnd((C, C), 604, scale=C ** -0.5)
     part = rnd((B, nsp, C, C), 605)
     dm = ops.reduce_parts(part, batched=True)
@@ -982,6 +1049,7 @@ def check_fold_bwd_split_dm(dev, dtype, C=64, heads=2, B=2, nsp=5):
         assert rel_l2(y, x.double().cpu()) < tol, rel_l2(y, x.double().cpu())
 
 
+@guarded
 def check_ln_bwd_win_dxn(dev, dtype, C=64, shape=(2, 16, 16), shift=4):
     """mphsir_ln_bwd_win_dxn (d_xn = dQKV Wqkv formed inside the LayerNorm-backward launch) against gemm_tok + ln_bwd_win on the same
     operands, and both against an fp64 evaluation (the fused form keeps d_xn in fp32: it must be no further from fp64 than the pair)"""
@@ -993,7 +1061,7 @@ def check_ln_bwd_win_dxn(dev, dtype, C=64, shape=(2, 16, 16), shift=4):
     x, dres = rnd((B, H, W, C), 921, dtype), rnd((B, H, W, C), 922, dtype)
     dqkv = rnd((M, 3 * C), 923, dtype)
     wT = rnd((C, 3 * C), 924, dtype, scale=(3 * C) ** -0.5)
-    ln_w = (1 + 0.2 * rnd((C,), 925)).contiguous()
+    ln_w = (rnd((C,), 925, scale=0.2, shift=1)).contiguous()
     dx_a, part_a = ops.ln_bwd_win(x, ops.gemm_tok(dqkv, wT), dres, ln_w, shift)
     dx_b, part_b = ops.ln_bwd_win_dxn(x, dqkv, wT, dres, ln_w, shift)
     # fp64: d_xn in window order -> image order through the same index map the oracle's window partition uses
@@ -1022,6 +1090,7 @@ def check_ln_bwd_win_dxn(dev, dtype, C=64, shape=(2, 16, 16), shift=4):
     return res
 
 
+@guarded
 def check_ln_bwd_tok_dxn(dev, dtype, C=64, K=384, M=256):
     """mphsir_ln_bwd_tok_dxn (token order, any K % 32 == 0, LN(x) as a second output) against gemm_tok + ln_bwd_tok on the same operands"""
     _use(dev)
@@ -1030,7 +1099,7 @@ def check_ln_bwd_tok_dxn(dev, dtype, C=64, K=384, M=256):
     x, dres = rnd((M, C), 931, dtype), rnd((M, C), 932, dtype)
     dy = rnd((M, K), 933, dtype)
     wT = rnd((C, K), 934, dtype, scale=K ** -0.5)
-    ln_w, ln_b = (1 + 0.2 * rnd((C,), 935)).contiguous(), (0.1 * rnd((C,), 936)).contiguous()
+    ln_w, ln_b = (rnd((C,), 935, scale=0.2, shift=1)).contiguous(), (rnd((C,), 936, scale=0.1)).contiguous()
     with ops.reduce_scope():
         a = ops.ln_bwd_tok(x, ops.gemm_tok(dy, wT), dres, ln_w, ln_b)
         b = ops.ln_bwd_tok_dxn(x, dy, wT, dres, ln_w, ln_b)
@@ -1065,6 +1134,7 @@ def check_ln_bwd_tok_dxn(dev, dtype, C=64, K=384, M=256):
     return res
 
 
+@guarded
 def check_fold_bwd_forms_dm(dev, dtype, C=64, heads=2, B=3, N=256):
     """mphsir_spectral_fold_bwd forming dM = d_out^T v itself (N > 0: the lower pyramid levels) against the token-reduction GEMM followed
     by the plain call, and dM against an fp64 product of the same operands"""
@@ -1074,14 +1144,14 @@ def check_fold_bwd_forms_dm(dev, dtype, C=64, heads=2, B=3, N=256):
     assert ops.fold_bwd_forms_dm(N, C, heads, dtype)
     gp = rnd((B, 1, heads, hd, hd), 611)
     sp = rnd((B, 1, 2, C), 612).abs() + 0.5
-    temp = (1 + 0.3 * rnd((heads,), 613)).contiguous()
+    temp = (rnd((heads,), 613, scale=0.3, shift=1)).contiguous()
     wo = rnd((C, C), 614, scale=C ** -0.5)
     d_out, v = rnd((B * N, C), 615, dtype), rnd((B * N, C), 616, dtype)
     dm = ops.gemm_tn(d_out.reshape(B, N, C), v.reshape(B, N, C), reduce=False)
     a = ops.spectral_fold_bwd(gp, sp, temp, wo, dm, dtype, reduce=False)
     b = ops.spectral_fold_bwd(gp, sp, temp, wo, None, dtype, reduce=False, d_out=d_out, v=v)
     # fp64 reference of W2 / dWo / dtemp through the plain call on an fp64-accurate dM
-    dm64 = torch.einsum("bnc,bnd->bcd", d_out.double().cpu().reshape(B, N, C), v.double().cpu().reshape(B, N, C)).float().to(dev)
+    dm64 = inp(torch.einsum("bnc,bnd->bcd", d_out.double().cpu().reshape(B, N, C), v.double().cpu().reshape(B, N, C)).float())
     c = ops.spectral_fold_bwd(gp, sp, temp, wo, dm64.contiguous(), dtype, reduce=False)
     res = {}
     for name, x, y, z in zip(("W2", "dWo", "dtemp"), a, b, c):
@@ -1095,7 +1165,7 @@ def check_fold_bwd_forms_dm(dev, dtype, C=64, heads=2, B=3, N=256):
         dM_ = kw.pop("dM")
         dense = ops.spectral_fold_bwd(gp, sp, temp, wo, dM_, dtype, reduce=False, **kw)
         blk = ops.spectral_fold_bwd(gp, sp, temp, wo, dM_, dtype, reduce=False, w2_blocks=True, **kw)
-        mask = torch.zeros((2 * C, 2 * C), dtype=torch.bool, device=dense[0].device)
+        mask = alloc((2 * C, 2 * C), torch.bool)
         for h in range(heads):
             for r0 in (h * hd, C + h * hd):
                 mask[r0:r0 + hd, h * hd:(h + 1) * hd] = True
@@ -1105,6 +1175,7 @@ def check_fold_bwd_forms_dm(dev, dtype, C=64, heads=2, B=3, N=256):
     return res
 
 
+@guarded
 def check_spectral_dqkv_bwd(dev, dtype, C, heads, shape, nblk=None):
     """mphsir_spectral_dqkv_bwd (dv, [dq | dk], depthwise backward + tap gradients in one launch) against the three launches it replaces
     -- gemm_tok(d_out, M_b^T), gemm_tok([q | k], W2), dwconv3x3_bwd -- on the same operands:
@@ -1118,19 +1189,19 @@ def check_spectral_dqkv_bwd(dev, dtype, C, heads, shape, nblk=None):
     M, hd = B * H * W, C // heads
     assert ops.spectral_dqkv_bwd_fits(C, heads, H, W, dtype), (C, heads, shape)
     qk, d_out, t = rnd((M, 2 * C), 901, dtype), rnd((M, C), 902, dtype), rnd((M, 3 * C), 903, dtype)
-    W2 = torch.zeros((B, 2 * C, 2 * C), dtype=torch.float32, device=dev)          # the block structure spectral_fold_bwd emits
+    W2 = alloc((B, 2 * C, 2 * C), role="input")          # the block structure spectral_fold_bwd emits
     full = rnd((B, 2 * C, 2 * C), 904, scale=(2 * hd) ** -0.5)
     for h in range(heads):
         qs, ks = slice(h * hd, (h + 1) * hd), slice(C + h * hd, C + (h + 1) * hd)
         W2[:, qs, ks] = full[:, qs, ks]
         W2[:, ks, qs] = full[:, ks, qs]
-    idx = torch.arange(2 * C, device=dev)
+    idx = inp(torch.arange(2 * C))
     W2[:, idx, idx] = full[:, idx, idx]
     W2 = W2.to(dtype).contiguous()
     MbT = rnd((B, C, C), 905, dtype, scale=C ** -0.5)
     w9 = rnd((9, 3 * C), 906, scale=1 / 3)
     # the three launches
-    dall = torch.empty((M, 3 * C), dtype=dtype, device=dev)
+    dall = alloc((M, 3 * C), dtype, fill=None)
     ops.gemm_tok(d_out, MbT, out=dall[:, 2 * C:])
     ops.gemm_tok(qk, W2, out=dall[:, :2 * C])
     with ops.reduce_scope():
@@ -1168,6 +1239,7 @@ def check_spectral_dqkv_bwd(dev, dtype, C, heads, shape, nblk=None):
     return res
 
 
+@guarded
 def check_channel_attention_bwd(dev, dtype, C, heads, shape, cross=False):
     """The channel ("spectral") attention backward chain -- gemm_tn (dM), spectral_fold_bwd, the [dq|dk] / dv token GEMMs,
     depthwise backward + tap gradients -- as the prompt modules use it (self: TransformerBlock :289-322; cross:
@@ -1177,7 +1249,7 @@ def check_channel_attention_bwd(dev, dtype, C, heads, shape, cross=False):
     from mp_hsir_amd import ops
     B, H, W = shape
     M = B * H * W
-    P = {"temperature": 1 + 0.3 * rnd((heads, 1, 1), 331), "project_out.weight": rnd((C, C, 1, 1), 332, scale=C ** -0.5)}
+    P = {"temperature": rnd((heads, 1, 1), 331, scale=0.3, shift=1), "project_out.weight": rnd((C, C, 1, 1), 332, scale=C ** -0.5)}
     if cross:
         P.update({"q.weight": rnd((C, C, 1, 1), 333, scale=C ** -0.5), "kv.weight": rnd((2 * C, C, 1, 1), 334, scale=C ** -0.5),
                   "q_dwconv.weight": rnd((C, 1, 3, 3), 335, scale=1 / 3), "kv_dwconv.weight": rnd((2 * C, 1, 3, 3), 336, scale=1 / 3)})
@@ -1242,6 +1314,7 @@ def check_channel_attention_bwd(dev, dtype, C, heads, shape, cross=False):
     return errs
 
 
+@guarded
 def check_channel_attention_bwd_refuses_layouts(dev, dtype=torch.float32, C=64, heads=2, shape=(1, 16, 16)):
     """The self entry point declares its layouts -- t one contiguous (B,H,W,3C), w9 one contiguous fp32 (9,3C) -- and raises on anything
     else BEFORE any launch: there is no slower path to fall to."""
@@ -1253,7 +1326,7 @@ def check_channel_attention_bwd_refuses_layouts(dev, dtype=torch.float32, C=64, 
     d_out, v = rnd((M, C), 341, dtype), rnd((M, C), 342, dtype)
     gp, sp = rnd((B, 1, heads, hd, hd), 343), rnd((B, 1, 2, C), 344).abs() + 1
     MbT = rnd((B, C, C), 345, dtype, scale=C ** -0.5)
-    temp, wo = 1 + 0.3 * rnd((heads, 1, 1), 346), rnd((C, C, 1, 1), 347, scale=C ** -0.5)
+    temp, wo = rnd((heads, 1, 1), 346, scale=0.3, shift=1), rnd((C, C, 1, 1), 347, scale=C ** -0.5)
     t, w9 = rnd((B, H, W, 3 * C), 348, dtype), rnd((9, 3 * C), 349, scale=1 / 3)
     wide_t, wide_w9 = rnd((B, H, W, 4 * C), 350, dtype), rnd((9, 4 * C), 351, scale=1 / 3)
     bad = {"t: pitch 4C": (wide_t[..., :3 * C], w9),
@@ -1275,6 +1348,7 @@ def check_channel_attention_bwd_refuses_layouts(dev, dtype=torch.float32, C=64, 
             ops.ACCOUNT = None
 
 
+@guarded
 def check_join_gradients(dev, shape=(1, 8, 16), C=32):
     """The joins that complete a buffer whose right half its producer already wrote (conv1x1(out=) -> _JoinLeft, conv3x3(out=) ->
     shuffle_join) against the same producers followed by torch.cat / pixel_shuffle2, fp32: the output and the gradients of both halves'
@@ -1292,7 +1366,7 @@ def check_join_gradients(dev, shape=(1, 8, 16), C=32):
         lshape = (B, H, W, C) if left == "plain" else (B, H // 2, W // 2, 4 * C)
         x, yin = rnd(lshape, 362).requires_grad_(True), rnd((B, H, W, C), 363).requires_grad_(True)
         if joined:
-            buf = torch.empty((B, H, W, 2 * C), dtype=torch.float32, device=dev)
+            buf = alloc((B, H, W, 2 * C), fill=None)
             p = produce(yin, conv, out=buf[..., C:])
             j = AG._JoinLeft.apply(x, p, buf) if left == "plain" else AG.shuffle_join(x, p, buf)
         else:
@@ -1306,6 +1380,7 @@ def check_join_gradients(dev, shape=(1, 8, 16), C=32):
             assert g is not None and g.shape == w.shape and torch.equal(g, w), (left, ksize, name, rel_l2(g, w))
 
 
+@guarded
 def check_loss_scaler(dev):
     """mphsir_grad_check / flat_adamw_scaled / scaler_update against torch.optim.AdamW + the GradScaler rules: a finite step equals
     AdamW on the unscaled gradient, an overflowing step changes nothing but halves the scale and restarts the streak (and
@@ -1314,7 +1389,7 @@ def check_loss_scaler(dev):
     from mp_hsir_amd import ops
     n = 4096
     p0 = rnd((n,), 401)
-    p, m, v = p0.clone(), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    p, m, v = alloc((n,), fill=None).copy_(p0), alloc((n,)), alloc((n,))
     ref = torch.nn.Parameter(p0.detach().cpu().clone())
     opt = torch.optim.AdamW([ref], lr=1e-2)
     sc = ops.new_loss_scaler(dev, 1024.0)
@@ -1337,12 +1412,13 @@ def check_loss_scaler(dev):
     assert float(sc[0]) == 1024.0 * 2 * 0.5 * 2 and float(sc[3]) == 4.0
 
 
+@guarded
 def check_layernorm_tok(dev, dtype, M=200, C=64):
     """mphsir_layernorm_tok (TVSP's norm11, net/MP_HSIR.py:282: fp32 rows in, compute dtype out) against F.layer_norm in fp64; the optional
     cast copy of the input BITWISE against .to(dtype); the vector form (C % 16 == 0) and the element-wise form (C % 4 == 0)"""
     _use(dev)
     from mp_hsir_amd import ops
-    lw, lb = (1 + 0.2 * rnd((C,), 521)).contiguous(), (0.1 * rnd((C,), 522)).contiguous()
+    lw, lb = (rnd((C,), 521, scale=0.2, shift=1)).contiguous(), (rnd((C,), 522, scale=0.1)).contiguous()
     for src in (torch.float32, dtype):
         x = rnd((M, C), 523, src)
         y, xc = ops.layernorm_tok(x, lw, lb, dtype, want_cast=True)
@@ -1352,6 +1428,7 @@ def check_layernorm_tok(dev, dtype, M=200, C=64):
         assert torch.equal(ops.layernorm_tok(x, lw, lb, dtype), y)
 
 
+@guarded
 def check_heads(dev, dtype, B=3, C=31, H=24, W=20, T=6, n=2):
     """heads.hip against the framework expressions they replace (net/MP_HSIR.py:519-527, :824, :842-843): the layout kernels BITWISE
     (one rounding each, the same one), the task-prompt algebra to fp32 rounding, forward and backward through the autograd wrappers."""
@@ -1378,7 +1455,7 @@ def check_heads(dev, dtype, B=3, C=31, H=24, W=20, T=6, n=2):
     AG._InputHead.apply(ig, dtype).backward(gx)
     assert torch.equal(ig.grad, gx[..., :C].permute(0, 3, 1, 2).to(torch.float32).contiguous())
     # task weights + weighted means
-    ids = torch.randint(0, T, (B, n), generator=torch.Generator().manual_seed(515)).to(dev)
+    ids = as_input(torch.randint(0, T, (B, n), generator=torch.Generator().manual_seed(515)))
     w = ops.task_weights(ids, T)
     wr = F.one_hot(ids, T).float().mean(dim=1)
     assert torch.equal(w, wr)
@@ -1393,6 +1470,7 @@ def check_heads(dev, dtype, B=3, C=31, H=24, W=20, T=6, n=2):
     assert table.grad.shape == table.shape and rel_l2(table.grad, tr.grad) < 1e-6
 
 
+@guarded
 def check_resamplers(dev, dtype, B=3, ps=16, D=32, H=40, W=24):
     """mphsir_tvsp_text_map (+bwd) against the reference's own expression (broadcast multiply + F.interpolate nearest,
     net/MP_HSIR.py:575-577) and mphsir_resize_bilinear (+bwd) against F.interpolate(bilinear) (:580), fp64 autograd."""
@@ -1415,3 +1493,64 @@ def check_resamplers(dev, dtype, B=3, ps=16, D=32, H=40, W=24):
     dy = rnd((B, H, W, D), 505, dtype)
     yr.backward(dy.double().cpu().permute(0, 3, 1, 2))
     assert rel_l2(ops.resize_bilinear(dy, ps, ps, backward=True), xd.grad.permute(0, 2, 3, 1)) < TOL[dtype]
+
+
+# ---- edge shapes: for each entry point the smallest shape its MPHSIR_REQUIREs and *_fits predicates accept, so that an overrun of one
+# tile falls into a guard band (tests/guard.py) rather than into the tensor, and one shape with a ragged tail where the kernel has one.
+# (name, check, args after (dev, dtype), kwargs, dtypes: None = fp32 + bf16, "half" = bf16 + fp16, "none" = the check takes no dtype)
+EDGE_CASES = [
+    ("gemm_tok_min", "gemm_tok", (64, 16, 32, False, 0), {}, None),                    # M % 64, N % 16, K % 32: one tile of each
+    ("gemm_tok_min_ln_res", "gemm_tok", (64, 16, 32, True, 1), {}, None),
+    ("gemm_tok_ring_min", "gemm_tok_ring", (64, 16, 32, 0), {}, "half"),               # fewer tiles than workgroups
+    ("gemm_tok_ring_res", "gemm_tok_ring", (256, 32, 32, 1), {}, "half"),
+    ("gated_mlp_min", "gated_mlp", (32, 85), dict(M=64), None),
+    ("gated_mlp_min_two_tiles", "gated_mlp", (32, 85), dict(M=64, tpw=2), None),
+    ("gated_mlp_min_eight_waves", "gated_mlp", (32, 85), dict(M=64, tpw=3), "half"),
+    ("gated_mlp_min_res", "gated_mlp", (32, 85), dict(M=64, res=True), None),
+    ("gated_mlp_bwd_min", "gated_mlp_bwd", (32, 85), dict(M=64), None),                # one 64-row tile: dx / xn / h / dpre / dm end with it
+    ("gated_mlp_bwd_min_variant1", "gated_mlp_bwd", (32, 85), dict(M=64, variant=1), None),
+    ("gated_mlp_bwd_min_variant3", "gated_mlp_bwd", (32, 85), dict(M=64, variant=3), None),
+    ("gated_mlp_bwd_min_variant4", "gated_mlp_bwd", (32, 85), dict(M=64, variant=4), None),
+    ("gated_mlp_bwd_min_hsplit", "gated_mlp_bwd", (96, 255), dict(M=64, hsplit=2), "half"),   # the fp32 partials dxn_part (hsplit, M, C)
+    ("dwconv_gram_one_row", "spectral_attention_chain", (32, 2, (1, 1, 64), 1), {}, None),      # H = 1: both halo rows outside the image
+    ("dwconv_gram_one_row_split", "spectral_attention_chain", (32, 2, (1, 1, 128), 2), {}, None),
+    ("dwconv_gram_8x8", "spectral_attention_chain", (32, 2, (1, 8, 8), 1), {}, None),
+    ("layernorm_one_row", "layernorm_tok", (), dict(M=1, C=4), None),
+    ("layernorm_63x20", "layernorm_tok", (), dict(M=63, C=20), None),
+    ("layernorm_65x16", "layernorm_tok", (), dict(M=65, C=16), None),
+    ("gemm_tn_one_row", "gemm_tn", (1, 8, 8, 1, 0), {}, None),
+    ("gemm_tn_8_rows", "gemm_tn", (8, 8, 8, 1, 0), {}, None),
+    ("gemm_tn_130_rows", "gemm_tn", (130, 8, 8, 2, 0), {}, None),
+    ("dwconv_one_row", "dwconv_plain", ((1, 1, 8, 32),), {}, None),                     # both halo rows lie outside the image
+    ("dwconv_8x8", "dwconv_plain", ((1, 8, 8, 32),), {}, None),
+    ("dwconv_one_row_c8", "dwconv_plain", ((1, 1, 8, 8),), {}, None),
+    ("conv3x3_64_tokens", "conv3x3", (1, 8, 8, 32, 16), {}, None),
+    ("combine_bwd_one_window", "combine_bwd", (), dict(C=64, shift=0, shape=(1, 8, 8)), None),
+    ("combine_bwd_one_window_shifted", "combine_bwd", (), dict(C=64, shift=4, shape=(1, 8, 8)), None),
+    ("ln_bwd_win_dxn_one_window", "ln_bwd_win_dxn", (), dict(C=64, shape=(1, 8, 8), shift=0), "half"),
+    ("ln_bwd_win_dxn_one_window_shifted", "ln_bwd_win_dxn", (), dict(C=64, shape=(1, 8, 8), shift=4), "half"),
+    ("win_attn_bwd_one_window", "win_attn_bwd_head_split", (), dict(C=64, heads=2, shape=(1, 8, 8)), "half"),
+    ("heads_one_channel", "heads", (), dict(B=1, C=1, H=8, W=8), None),
+    ("heads_172_channels", "heads", (), dict(B=1, C=172, H=8, W=8, T=7, n=1), None),
+    ("resamplers_min", "resamplers", (), dict(B=1, ps=2, D=8, H=4, W=4), None),           # D = 8: one 16-byte vector of a 16-bit row
+    ("pg_gate_fwd_one_window", "pg_gate_fwd", (128, 8), dict(nW=1), "none"),
+    ("pg_gate_fwd_17_windows", "pg_gate_fwd", (128, 8), dict(nW=17), "none"),
+    ("pg_gate_bwd_one_window", "pg_gate_bwd", (128, 8), dict(nW=1), "none"),
+    ("pg_gate_bwd_17_windows", "pg_gate_bwd", (128, 8), dict(nW=17), "none"),
+    ("reduce_block_one_row", "reduce_block", (), {}, "none"),
+]
+WIN_EDGE_CASES = [("tiny", "encoder_level1.blocks.1.", 1, 0, (1, 8, 8, 32)), ("tiny", "encoder_level1.blocks.1.", 1, 4, (1, 8, 8, 32))]      # a single window
+
+
+def edge_params():
+    """(id, check name, args, kwargs, dtype or None) for pytest.mark.parametrize, the dtypes expanded"""
+    out = []
+    for name, fn, a, kw, dts in EDGE_CASES:
+        for dt in {None: DTYPES, "half": [torch.bfloat16, torch.float16], "none": [None]}[dts]:
+            out.append((name + ("" if dt is None else "-" + str(dt).replace("torch.", "")), fn, a, kw, dt))
+    return out
+
+
+def run_edge(dev, fn, a, kw, dt):
+    check = globals()["check_" + fn]
+    return check(dev, *a, **kw) if dt is None else check(dev, dt, *a, **kw)

@@ -39,3 +39,10 @@ def test_block_backward_switch_on_and_off(name, shift):
 @pytest.mark.parametrize("name", BB.BLOCK_NAMES)
 def test_block_backward_deterministic(name, shift):
     BB.check_block_deterministic("cuda", torch.bfloat16, name, shift)
+
+
+@pytest.mark.parametrize("dtype", HALF)
+@pytest.mark.parametrize("shift", [0, 4])
+def test_win_attn_bwd_dsa_prologue_single_window(dtype, shift):
+    """the smallest accepted shape, one 8x8 window: an overrun of one window lands in a guard band (tests/guard.py), not in the tensor"""
+    BB.check_dsa_prologue("cuda", dtype, 64, 2, shift, shape=(1, 8, 8))

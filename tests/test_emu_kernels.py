@@ -380,3 +380,28 @@ def test_gated_mlp_second_residual(dtype):
     if dtype != torch.float32:
         K.check_gated_mlp("cpu", dtype, 128, 340, tpw=3, M=256, res=True)
         K.check_gated_mlp("cpu", dtype, 256, 680, M=256, hsplit=2, res=True)
+
+
+# ---- edge shapes under the guard bands (kernel_checks.EDGE_CASES): the smallest shape every entry point accepts + ragged tails ----
+_EDGE = K.edge_params()
+
+
+@pytest.mark.parametrize("fn,a,kw,dt", [e[1:] for e in _EDGE], ids=[e[0] for e in _EDGE])
+def test_edge_shapes(fn, a, kw, dt):
+    K.run_edge("cpu", fn, a, kw, dt)
+
+
+@pytest.mark.parametrize("dtype", K.DTYPES)
+@pytest.mark.parametrize("man,prefix,heads,shift,shape", K.WIN_EDGE_CASES)
+def test_win_attn_single_window(dtype, man, prefix, heads, shift, shape, manifest):
+    K.check_win_attn("cpu", dtype, man, prefix, heads, shift, shape, manifest)
+
+
+def test_guard_was_active():
+    """the checks above ran under tests/guard.py: a check allocates through it and the counters move"""
+    import guard
+    before = list(guard.STATS.get("kernel_checks", [0, 0, {}]))
+    K.check_layernorm_tok("cpu", torch.float32, M=1, C=4)
+    after = guard.STATS["kernel_checks"]
+    assert after[0] == before[0] + 1 and after[1] >= before[1] + 10, (before, after)
+    print("guard: kernel_checks: %d guarded checks, %d guarded allocations so far" % tuple(after[:2]))
