@@ -948,6 +948,49 @@ int mphsir_multi_copy(const int64_t* table_dev, int32_t nseg, int64_t total_bloc
  * the loss), grad (optional) = d loss / d y = sign(clamp(y) - clean) / n where 0 <= y <= 1, else 0.  fp32, contiguous.      */
 int mphsir_l1_clamp_loss(const float* y, const float* clean, float* grad, float* part, int64_t n, int32_t nblocks, void* stream);
 
+/* ---- training loss with spectral terms: L1 + w_sam * SAM + w_sdiff * SDIFF and its gradient, one launch pair (off unless the caller
+ * asks: mp-hsir_amd/engine.py SpectralLoss) ----------------------------------------------------------------------------------------
+ * y (restored) and clean: fp32, contiguous (B, C, H, W).  x = clamp(y, 0, 1) with mphsir_l1_clamp_loss's NaN-propagating clamp,
+ * m = [0 <= y <= 1] (bounds included), P = B H W, sign(0) = 0.
+ *   L1    = sum |x - c| / (B C H W)                                   d L1 / d y_k = sign(x_k - c_k) m_k / (B C H W)
+ *   SAM   = (1 / P) sum over pixels of theta, in radians.  Per pixel, over all C bands: nx = |x|, ny = |c|, d2 = |x - c|^2,
+ *           theta = 2 atan2(sqrt(max(d2 - (nx - ny)^2, 0)), sqrt(max((nx + ny)^2 - d2, 0)))    (the form of mphsir_quality);
+ *           a pixel with nx == 0 or ny == 0 contributes 0; the divisor stays P.
+ *           d SAM / d y_k = -(a c_k - b x_k) m_k / P with a = 1 / (sin nx ny), b = cos / (sin nx^2), where sin and cos are those of
+ *           theta, formed without a call from the two square roots s, t above: sin = 2 s t / (s^2 + t^2), cos = (t^2 - s^2) / (s^2 + t^2).
+ *           The gradient of the WHOLE pixel is 0 when sin < MPHSIR_SAM_MIN_SIN, when a norm is 0 or when a pixel sum is not finite
+ *           (its norm is 1 / nx: bounded; only its direction is undefined at theta = 0, and 0 is the subgradient taken there).
+ *   SDIFF = sum |e| / (B (C - 1) H W), e_k = (x_{k+1} - x_k) - (c_{k+1} - c_k), k = 0 .. C - 2; 0 with zero gradient at C = 1.
+ *           d SDIFF / d y_k = (sign(e_{k-1}) - sign(e_k)) m_k / (B (C - 1) H W), a missing neighbour's sign taken as 0.
+ *   loss  = L1 + w_sam SAM + w_sdiff SDIFF;   grad (optional, fp32, the shape of y) = d loss / d y.
+ * out: four fp32 values on the device, {loss, L1, SAM in radians, SDIFF}.  A weight of 0 skips its term: the component is written
+ * as 0 and the gradient holds nothing of it.  A NaN in y makes the loss NaN; the gradient entry of that element is 0.
+ * Arithmetic: the per-pixel sums, theta, a, b and every sum of the three terms in float64 (a product of two fp32 values is exact
+ * there); a c_k - b x_k, the two constants of L1 and SDIFF and the two additions that join the terms in fp32.  Launch 1 (a
+ * workgroup owns 256 pixels of one image, its four waves a quarter of the bands each; per-pixel sums combined in wave order) writes
+ * grad and three float64 partials per workgroup to `workspace`; launch 2 (one workgroup) adds them in a fixed order and writes `out`.
+ * No atomics, nothing read back, nothing zero-filled: capturable, bitwise equal from run to run and -- every pixel's arithmetic is
+ * the same on both -- between the 16-byte path (W % 4 == 0 and y, clean, grad 16-byte aligned) and the scalar path.
+ * workspace: mphsir_spectral_loss_workspace_bytes(B, C, H, W) bytes, 8-byte aligned, caller-owned (negative: sizes refused).
+ * Refused (MPHSIR_EINVAL, nothing launched): another struct_size; a null y / clean / out / workspace; B, C, H or W < 1 or more than
+ * 2^31 - 1 workgroups; a weight that is negative or not finite; both weights 0 (that loss is mphsir_l1_clamp_loss); a workspace that is
+ * too small or not 8-byte aligned.  (Declared as `struct ...; typedef ...;` like the optimizer structs: it has float members.)      */
+#define MPHSIR_SAM_MIN_SIN 1e-6
+struct mphsir_spectral_loss_args {
+    uint32_t struct_size;       /* = sizeof(this struct), set by the caller: any other value is rejected with MPHSIR_EINVAL */
+    const float* y;
+    const float* clean;
+    float* grad;
+    float* out;
+    void* workspace;
+    int64_t workspace_bytes;
+    int32_t B, C, H, W;
+    float w_sam, w_sdiff;
+};
+typedef struct mphsir_spectral_loss_args mphsir_spectral_loss_args;
+int64_t mphsir_spectral_loss_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int mphsir_spectral_loss(const mphsir_spectral_loss_args* a, void* stream);
+
 /* ---- optional per-kernel launch timer (bench.py roofline leg) ----------------------------------
  * When enabled for kernel id `kid`, every launch of that kernel is bracketed by hipEvents on its
  * own stream.  read(): synchronises the recorded events, returns the number of launches and their
@@ -991,7 +1034,9 @@ int mphsir_l1_clamp_loss(const float* y, const float* clean, float* grad, float*
 #define MPHSIR_K_PATCH_NORMALISE 36   /* launch 2 (combine + normalise): ids of their own, so that the timer tells the two apart */
 #define MPHSIR_K_CASSI_MEASURE 37     /* launch 1 of mphsir_cassi (measurement rows + block min / max) */
 #define MPHSIR_K_CASSI_EMIT 38        /* launch 2 (combine + normalise + flip / rotation) */
-#define MPHSIR_K_COUNT 39
+#define MPHSIR_K_SPECTRAL_LOSS 39         /* launch 1 of mphsir_spectral_loss (gradient + block partials) */
+#define MPHSIR_K_SPECTRAL_LOSS_FINISH 40  /* launch 2 (ordered sum of the partials -> out) */
+#define MPHSIR_K_COUNT 41
 int mphsir_prof_enable(int kid);   /* kid < 0 disables */
 int mphsir_prof_read(int* launches, float* total_ms);
 const char* mphsir_kernel_name(int kid);

@@ -196,6 +196,12 @@ class FlatAdamwExArgs(_Args):
                [("step", c_int32), ("ema_decay", ctypes.c_float)] + [(n, c_void_p) for n in ("hyper", "scaler", "stats")]
 
 
+class SpectralLossArgs(_Args):
+    """ctypes image of mphsir_spectral_loss_args (float members: compared with the header by tests/test_spectral_loss_meta.py)"""
+    _fields_ = _SZ + [(n, c_void_p) for n in ("y", "clean", "grad", "out", "workspace")] + [("workspace_bytes", c_int64)] + \
+               [(n, c_int32) for n in ("B", "C", "H", "W")] + [("w_sam", ctypes.c_float), ("w_sdiff", ctypes.c_float)]
+
+
 class TnProblem(ctypes.Structure):
     """mirror of struct mphsir_gemm_tn_problem"""
     _fields_ = [("A", c_void_p), ("lda", c_int64), ("B", c_void_p), ("ldb", c_int64), ("Cpart", c_void_p), ("colsum_part", c_void_p),
@@ -311,6 +317,8 @@ _SYMBOLS = {
     "mphsir_cassi_workspace_bytes": (c_int64, [c_int32] * 5),
     "mphsir_cassi": (c_int, [ctypes.POINTER(CassiArgs), c_void_p]),
     "mphsir_l1_clamp_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    "mphsir_spectral_loss_workspace_bytes": (c_int64, [c_int32] * 4),
+    "mphsir_spectral_loss": (c_int, [ctypes.POINTER(SpectralLossArgs), c_void_p]),
 }
 
 

@@ -32,6 +32,24 @@ def l1_after_clamp(restored, clean):
     return ops.l1_clamp_loss(restored.float(), clean.float())
 
 
+class SpectralLoss:
+    """loss_fn with spectral terms: l1_after_clamp + sam * (mean spectral angle, radians) + sdiff * (L1 of band-to-band differences), one
+    launch pair for the loss and its gradient (ops.spectral_loss; the definitions: include/mphsir.h).  Off unless handed to the engine:
+    `DataParallelEngine(net, lr, loss_fn=SpectralLoss(sam=0.1))`."""
+
+    def __init__(self, sam=0.0, sdiff=0.0):
+        sam, sdiff = float(sam), float(sdiff)
+        assert 0.0 <= sam < float("inf") and 0.0 <= sdiff < float("inf"), "SpectralLoss: weights must be finite and >= 0, got %r / %r" % (sam, sdiff)
+        assert sam > 0.0 or sdiff > 0.0, "SpectralLoss: both weights are 0 -- that loss is l1_after_clamp"
+        self.sam, self.sdiff = sam, sdiff
+
+    def __call__(self, restored, clean):
+        return ops.spectral_loss(restored.float(), clean.float(), self.sam, self.sdiff)
+
+    def weights(self):
+        return {"sam": self.sam, "sdiff": self.sdiff}
+
+
 class PackPlan:
     """All kernel-layout weights of the model as ONE gather from the flat fp32 parameter arena.
 
@@ -215,7 +233,14 @@ class DataParallelEngine:
         assert ema_decay is None or 0.0 <= ema_decay < 1.0, "ema_decay must lie in [0, 1) (None: off), got %r" % (ema_decay,)
         self.grad_clip, self.ema_decay, self.ema_warmup = grad_clip, ema_decay, ema_warmup
         self.flat_ema = self.optim_stats = self._gn_ws = None
-        if self.world > 1:      # DDP's initial parameter broadcast (rank 0 -> all), one flat message
+        self._loss_parts = None         # SpectralLoss: the device fp32[4] {loss, L1, SAM, SDIFF} of the last step (graph mode: the replayed buffer)
+        # An eager step of the default loss hands the optimizer kernel lr and the step number, and the library forms Adam's bias corrections
+        # with fp32 powf; a replayed step reads [lr, 1 - beta1^t, sqrt(1 - beta2^t)] that the host formed in float64 (1 - 0.9f = 0.100000024
+        # against fp32(1 - 0.9) = 0.1 at t = 1): eager and graph mode differ in the last bits from the first replayed step on.  That is what
+        # the default path has always computed and it stays.  Under a SpectralLoss the eager step stages the same scalars on the device, so
+        # that eager and graph mode train bitwise the same parameters.
+        self._eager_hyper = isinstance(loss_fn, SpectralLoss)
+        if self.world > 1:     # DDP's initial parameter broadcast (rank 0 -> all), one flat message
             ps = [p for p in net.parameters()]
             flat = torch.cat([p.data.reshape(-1).float() for p in ps])
             dist.broadcast(flat, 0, group=self.pg)
@@ -364,9 +389,13 @@ class DataParallelEngine:
         """loss + backward pass -> the (unscaled) loss.  With the reference's own loss (l1_after_clamp, train.py:58-61) the loss kernel's
         gradient starts the backward pass at `restored` directly: `loss.backward()` would first build a ones_like tensor and scale the
         gradient by it (two launches; with the fp16 loss scale three)."""
-        if (self.loss_fn is l1_after_clamp and restored.dtype == torch.float32 and clean.dtype == torch.float32
-                and restored.shape == clean.shape and restored.requires_grad):
-            loss, g = ops.l1_clamp_loss_grad(restored.detach(), clean)
+        spectral = isinstance(self.loss_fn, SpectralLoss)
+        if ((spectral or self.loss_fn is l1_after_clamp) and restored.dtype == torch.float32 and clean.dtype == torch.float32
+                and restored.shape == clean.shape and restored.requires_grad and (not spectral or restored.dim() == 4)):
+            if spectral:
+                loss, g, self._loss_parts = ops.spectral_loss_grad(restored.detach(), clean, self.loss_fn.sam, self.loss_fn.sdiff)
+            else:
+                loss, g = ops.l1_clamp_loss_grad(restored.detach(), clean)
             if self._use_scaler(restored.device):
                 g.mul_(self.scaler[0])
             with ops.deferred_reductions():
@@ -576,6 +605,15 @@ class DataParallelEngine:
         s = self.optim_stats.detach().cpu().tolist()
         return {"norm": s[0], "coef": s[1], "skipped": int(s[2])}
 
+    def loss_components(self):
+        """{'loss', 'l1', 'sam_deg', 'sdiff'} of the last step under a SpectralLoss (None under any other loss, or before the first
+        step): the unweighted terms, the spectral angle in degrees.  ONE device-to-host transfer: call it when logging, not every step."""
+        if self._loss_parts is None:
+            return None
+        import math
+        v = self._loss_parts.detach().cpu().tolist()
+        return {"loss": v[0], "l1": v[1], "sam_deg": math.degrees(v[2]), "sdiff": v[3]}
+
     def ema_state_dict(self):
         """the network's state_dict() with the EMA value in place of every arena parameter; buffers and parameters without a gradient
         keep their live values"""
@@ -641,7 +679,11 @@ class DataParallelEngine:
             h.wait()
         self._pending = []
         self.step_count += 1
-        self._optimizer_step(self.lr if lr is None else lr)
+        if self._eager_hyper:
+            hyper = torch.tensor(self._hyper_values(self.lr if lr is None else lr, self.step_count), dtype=torch.float32, device=self.flat_p.device)
+            self._optimizer_step(None, hyper=hyper)
+        else:
+            self._optimizer_step(self.lr if lr is None else lr)
         if self.plan is not None:
             self.plan.refresh()
         return loss.detach()

@@ -511,6 +511,75 @@ def l1_clamp_loss_grad(y, clean):
     return _l1_clamp_loss_launch(y, clean, True)
 
 
+_SPECTRAL_WS = {}      # (device, stream, bytes) -> the float64 block partials of mphsir_spectral_loss, reused from call to call
+
+
+def spectral_loss_workspace(y):
+    """the workspace mphsir_spectral_loss needs for a (B,C,H,W) cube like y, one per (device, stream, size): launch 2 has consumed it
+    when the call returns to the stream, so the next call on that stream may overwrite it"""
+    B, C, H, W = y.shape
+    nbytes = _lib.load().mphsir_spectral_loss_workspace_bytes(B, C, H, W)
+    if nbytes < 0:
+        raise RuntimeError("mp-hsir_amd: spectral_loss refuses (B %d, C %d, H %d, W %d)" % (B, C, H, W))
+    key = (y.device, torch.cuda.current_stream(y.device).cuda_stream if y.is_cuda else 0, nbytes)
+    ws = _SPECTRAL_WS.get(key)
+    if ws is None:
+        ws = _SPECTRAL_WS[key] = torch.empty((nbytes // 8,), dtype=torch.float64, device=y.device)
+    return ws
+
+
+def _spectral_loss_launch(y, clean, w_sam, w_sdiff, want_grad):
+    """one launch pair: -> (fp32[4] {loss, L1, SAM in radians, SDIFF} on the device, d loss / d y or None); include/mphsir.h holds the
+    definition of loss = L1 + w_sam SAM + w_sdiff SDIFF"""
+    lib = _lib.load()
+    _check(y, clean)
+    assert y.dtype == torch.float32 and clean.dtype == torch.float32, "spectral_loss: fp32 inputs, got %s / %s" % (y.dtype, clean.dtype)
+    assert y.dim() == 4 and y.shape == clean.shape and y.device == clean.device, "spectral_loss: two (B,C,H,W) cubes of one shape on one device"
+    w_sam, w_sdiff = float(w_sam), float(w_sdiff)
+    if not (0.0 <= w_sam < float("inf") and 0.0 <= w_sdiff < float("inf")):
+        raise RuntimeError("mp-hsir_amd: spectral_loss: the weights must be finite and >= 0, got %r / %r" % (w_sam, w_sdiff))
+    if w_sam == 0.0 and w_sdiff == 0.0:
+        raise RuntimeError("mp-hsir_amd: spectral_loss: both weights are 0 -- that loss is l1_clamp_loss")
+    y, clean = y.contiguous(), clean.contiguous()
+    B, C, H, W = y.shape
+    ws = spectral_loss_workspace(y)
+    g = torch.empty_like(y) if want_grad else None
+    out = torch.empty((4,), dtype=torch.float32, device=y.device)
+    a = _lib.SpectralLossArgs(y=_p(y), clean=_p(clean), grad=_p(g), out=_p(out), workspace=_p(ws), workspace_bytes=8 * ws.numel(),
+                              B=B, C=C, H=H, W=W, w_sam=w_sam, w_sdiff=w_sdiff)
+    _lib.check(lib.mphsir_spectral_loss(ctypes.byref(a), _stream(y)), "spectral_loss")
+    n = float(y.numel())
+    _acct("spectral_loss", 14.0 * n, 4.0 * n * (5 if want_grad else 2))       # walk 2 reads both cubes again (from cache) and writes grad
+    return out, g
+
+
+class _SpectralLoss(torch.autograd.Function):
+    """L1 + w_sam SAM + w_sdiff SDIFF of clamp(y, 0, 1) against clean with its gradient from the same launch (mphsir_spectral_loss)"""
+
+    @staticmethod
+    def forward(ctx, y, clean, w_sam, w_sdiff):
+        out, ctx.g = _spectral_loss_launch(y, clean, w_sam, w_sdiff, ctx.needs_input_grad[0])
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        g, ctx.g = ctx.g, None
+        assert g is not None, "spectral_loss: its gradient buffer is scaled in place and handed over: backward() runs once"
+        return g.mul_(dloss), None, None, None
+
+
+def spectral_loss(y, clean, w_sam, w_sdiff):
+    """the training loss with spectral terms as a 0-d tensor, differentiable w.r.t. y"""
+    return _SpectralLoss.apply(y, clean, w_sam, w_sdiff)
+
+
+def spectral_loss_grad(y, clean, w_sam, w_sdiff):
+    """(loss, its gradient w.r.t. y, components = fp32[4] {loss, L1, SAM in radians, SDIFF}) from one launch pair, outside autograd: for
+    a caller that starts the backward pass at y itself (engine.DataParallelEngine)"""
+    out, g = _spectral_loss_launch(y, clean, w_sam, w_sdiff, True)
+    return out[0], g, out
+
+
 def _rows(t):
     """(rows, ld) of a 2-D view whose last dim is contiguous."""
     assert t.dim() == 2 and t.stride(1) == 1, "expected a row-major 2-D view"

@@ -6,7 +6,7 @@ options.py (options.py:6-37), so its command lines (README.md:36,38) work unchan
 Like the reference, the namespace is built at import time (`from options import options as opt`);
 unknown flags are tolerated so that importing this module under pytest/torchrun does not abort.
 Additions (not present in the reference, all optional): --model, --precision, --steps_per_epoch, --graph,
---synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade, --scene_dir, --crop_jitter, --grad_clip, --ema_decay, --task_classes, --cassi_mask, --cassi_step.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
+--synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade, --scene_dir, --crop_jitter, --grad_clip, --ema_decay, --task_classes, --cassi_mask, --cassi_step, --loss_sam, --loss_sdiff.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
 into ['0','1'] (options.py:36) and `--classifier type=bool` treats any non-empty string as True.
 --fused_degrade 1 works at every --patch_size: a patch of up to 128 x 128 is degraded by the plane form of the launch, a larger one (256
 out of a --scene_dir store, say) by its tiled form, with the same plan and the same element values.
@@ -68,6 +68,9 @@ _FLAGS = [
     ("--cassi_step", dict(type=int, default=2, help="'cassi' degradation: dispersion step in columns per band (the reference: 2)")),
     ("--ema_decay", dict(type=float, default=0.0, help="> 0: keep an exponential moving average of the weights with this decay (warmed up as "
                          "min(decay, (1 + t) / (10 + t))), saved as `state_dict_ema` and evaluated by test.py --use_ema 1; 0 (default): off")),
+    ("--loss_sam", dict(type=float, default=0.0, help="> 0: add this weight times the mean spectral angle (radians) of the restored patch against the "
+                        "clean one to the clamp + L1 loss (engine.SpectralLoss, one fused launch pair); 0 (default): off")),
+    ("--loss_sdiff", dict(type=float, default=0.0, help="> 0: add this weight times the L1 of the band-to-band differences; 0 (default): off")),
 ]
 
 

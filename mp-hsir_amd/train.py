@@ -16,6 +16,9 @@ the origins).  Either way the per-task degradations of --*_single_de_type are sy
 (degrade.DegradationSynthesizer).  Checkpoints carry, besides the `net.`-prefixed state_dict, AdamW's moments and step
 count and the CLIP text-embedding table the model was built with.  --ckpt_path is the reference's warm start (weights whose
 key and shape match, epoch 0); --resume 1 additionally restores the optimizer state and continues at the saved epoch + 1.
+--loss_sam F / --loss_sdiff F (both 0 by default: the reference's loss) add the mean spectral angle and the L1 of band-to-band
+differences to the loss (engine.SpectralLoss); the log line then ends with the unweighted terms, checkpoints carry the weights as
+`mphsir_loss` and --resume 1 says so when the run's weights differ from the file's.
 """
 import os
 import random
@@ -29,7 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from mp_hsir_amd import degrade  # noqa: E402
 from mp_hsir_amd.data import REMOTE_SENSING_SOURCES, PatchDB, PatchDBSource, SceneStoreSource, SyntheticPatchSource  # noqa: E402
-from mp_hsir_amd.engine import DataParallelEngine, warmup_cosine_lr  # noqa: E402
+from mp_hsir_amd.engine import DataParallelEngine, SpectralLoss, warmup_cosine_lr  # noqa: E402
 from mp_hsir_amd.net.MP_HSIR import _TASK_PROMPTS, MP_HSIR_Net  # noqa: E402
 from mp_hsir_amd.options import options as opt  # noqa: E402
 from mp_hsir_amd.scene_store import SceneStore, scene_files  # noqa: E402
@@ -78,7 +81,17 @@ def load_warm_start(net, path, device, engine=None, resume=False):
                                % (path if not isinstance(path, dict) else "this one"))
         engine.load_optimizer_state(ckpt["mphsir_optimizer"])          # with --ema_decay: the EMA too (a state without one starts it from the weights)
         resume_epoch = int(ckpt.get("epoch", -1)) + 1
+        was, now = ckpt.get("mphsir_loss") or {"sam": 0.0, "sdiff": 0.0}, loss_weights(engine)
+        if was != now:
+            print("note: the checkpoint was trained with loss weights sam %g sdiff %g, this run continues with sam %g sdiff %g"
+                  % (was["sam"], was["sdiff"], now["sam"], now["sdiff"]), flush=True)
     return len(kept), resume_epoch
+
+
+def loss_weights(engine):
+    """the weights of the spectral terms of the engine's loss ({"sam": 0, "sdiff": 0}: the reference's clamp + L1)"""
+    fn = getattr(engine, "loss_fn", None)
+    return fn.weights() if isinstance(fn, SpectralLoss) else {"sam": 0.0, "sdiff": 0.0}
 
 
 def save_checkpoint(path, net, engine, epoch):
@@ -86,7 +99,7 @@ def save_checkpoint(path, net, engine, epoch):
     `state_dict_ema` holds them in the same layout (test.py --use_ema 1)."""
     ckpt = {"state_dict": {"net." + k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, "epoch": epoch,
             "mphsir_optimizer": engine.optimizer_state(), "mphsir_clip_prompt": net.clip_prompts.detach().cpu().clone(),
-            "mphsir_clip_source": net.text_prompt.clip_source}
+            "mphsir_clip_source": net.text_prompt.clip_source, "mphsir_loss": loss_weights(engine)}
     if getattr(engine, "ema_decay", None) is not None:
         ckpt["state_dict_ema"] = {"net." + k: v.detach().cpu().clone() for k, v in engine.ema_state_dict().items()}
     torch.save(ckpt, path)
@@ -113,8 +126,12 @@ def main():
     dtypes = {"bf16": torch.bfloat16, "f32": torch.float32, "f16": torch.float16}
     net = MP_HSIR_Net(**cfg, clip_prompt=clip_prompt, compute_dtype=dtypes[opt.precision]).to(dev).train()
     extras = opt.grad_clip > 0 or opt.ema_decay > 0
+    if opt.loss_sam < 0 or opt.loss_sdiff < 0:
+        raise SystemExit("--loss_sam / --loss_sdiff must be >= 0 (0: the term is off)")
+    spectral = opt.loss_sam > 0 or opt.loss_sdiff > 0          # off: the engine's default loss, the launches and the log lines of always
     eng = DataParallelEngine(net, lr=opt.lr, use_graph=bool(opt.graph), grad_clip=opt.grad_clip if opt.grad_clip > 0 else (float("inf") if extras else None),     # EMA alone: measure the norm for the log
-                             ema_decay=opt.ema_decay if opt.ema_decay > 0 else None)
+                             ema_decay=opt.ema_decay if opt.ema_decay > 0 else None,
+                             **(dict(loss_fn=SpectralLoss(opt.loss_sam, opt.loss_sdiff)) if spectral else {}))
     start_epoch = 0
     if opt.ckpt_path is not None:
         n, start_epoch = load_warm_start(net, ckpt, dev, eng, resume=bool(opt.resume))
@@ -173,11 +190,15 @@ def main():
                 if world > 1:
                     dist.all_reduce(loss, op=dist.ReduceOp.AVG)       # self.log(..., sync_dist=True), train.py:65
                 running = float(loss)
+                parts = ""
+                if rank == 0 and spectral:          # one more small read-back per logged step: this rank's unweighted terms
+                    lc = eng.loss_components()
+                    parts = " l1 %.5f sam_deg %.4f sdiff %.5f" % (lc["l1"], lc["sam_deg"], lc["sdiff"])
                 if rank == 0 and extras:
                     gst = eng.grad_stats()          # one small read-back per logged step (the norm is the unclipped one)
-                    print("epoch %d it %d lr %.3e grad_norm %.4f clip %.3f train_loss %.5f" % (epoch, it + 1, lr, gst["norm"], gst["coef"], running), flush=True)
+                    print("epoch %d it %d lr %.3e grad_norm %.4f clip %.3f train_loss %.5f%s" % (epoch, it + 1, lr, gst["norm"], gst["coef"], running, parts), flush=True)
                 elif rank == 0:
-                    print("epoch %d it %d lr %.3e train_loss %.5f" % (epoch, it + 1, lr, running), flush=True)
+                    print("epoch %d it %d lr %.3e train_loss %.5f%s" % (epoch, it + 1, lr, running, parts), flush=True)
         if rank == 0 and opt.ckpt_dir and (epoch + 1) % 50 == 0:      # ModelCheckpoint(every_n_epochs=50), train.py:104
             os.makedirs(opt.ckpt_dir, exist_ok=True)
             save_checkpoint(os.path.join(opt.ckpt_dir, "epoch=%d.ckpt" % epoch), net, eng, epoch)
