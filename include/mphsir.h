@@ -651,6 +651,32 @@ typedef struct mphsir_quality_args {
 int64_t mphsir_quality_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
 int mphsir_quality(const mphsir_quality_args* a, void* stream);
 
+/* ---- quality meter: the outputs of mphsir_quality for one batch added to a row of running sums, one launch, nothing read back ------------
+ * psnr, ssim [B][C], sam_deg [B], sam_pixels [B]: as mphsir_quality wrote them (sam_pixels is part of that interface and is not read).
+ * use [B][C] uint8 or NULL: the bands of an image that count (NULL: all of them -- band completion scores the completed bands only).
+ * The first n <= B images count (the last batch of a set is padded).  table: float64 [rows][8]; the launch updates row `row`:
+ *   [0] images scored            [1] sum of per-image PSNR      [2] sum of per-image SSIM     [3] sum of per-image SAM (degrees)
+ *   [4] images set aside as non-finite      [5] min per-image PSNR     [6] max per-image PSNR     [7] images without a used band (skipped)
+ * reset != 0 first sets the row to {0, 0, 0, 0, 0, +inf, -inf, 0}; otherwise the launch adds onto what the row holds.
+ * Per image: PSNR and SSIM are the sum over its used bands in ascending band order divided by their number, SAM is sam_deg[b].  An
+ * image without a used band goes to [7]; one whose PSNR mean, SSIM mean or SAM is not finite (a NaN in a used band, a perfectly
+ * restored band with psnr = +inf) goes to [4]; neither enters a sum.  A value in an unused band is never read into a sum.  Images are
+ * added in ascending image order, so the row after a set is a function of the sequence of per-image values alone -- the same bits
+ * however the set was cut into batches -- and is reproducible from run to run (no atomics; one workgroup: threads own images for the
+ * band walk, one thread adds the images).  Refused, nothing launched: a null pointer (use may be NULL), n outside [0, B], row outside
+ * [0, rows), B, C or rows < 1.                                                                                                       */
+typedef struct mphsir_quality_meter_args {
+    uint32_t struct_size;
+    const double* psnr;
+    const double* ssim;
+    const double* sam_deg;
+    const int64_t* sam_pixels;
+    const uint8_t* use;
+    double* table;
+    int32_t B, C, n, rows, row, reset;
+} mphsir_quality_meter_args;
+int mphsir_quality_meter(const mphsir_quality_meter_args* a, void* stream);
+
 /* ---- training-batch degradation: clean batch -> (degraded, clean under the same flip / rotation) in ONE launch ---------------------------
  * The element values are those of the tensor functions of mp-hsir_amd/degrade.py (the reference's utils/degradation_utils.py:25-293 and
  * data_augmentation, utils/image_utils.py:141-176), which stay the definition; the launch is a pure function of the clean batch, the plan

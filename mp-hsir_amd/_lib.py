@@ -162,6 +162,12 @@ class QualityArgs(_Args):
                [("workspace_bytes", c_int64)] + [(n, c_int32) for n in ("B", "C", "H", "W")]
 
 
+class QualityMeterArgs(_Args):
+    """mirror of struct mphsir_quality_meter_args"""
+    _fields_ = _SZ + [(n, c_void_p) for n in ("psnr", "ssim", "sam_deg", "sam_pixels", "use", "table")] + \
+               [(n, c_int32) for n in ("B", "C", "n", "rows", "row", "reset")]
+
+
 class DegradeArgs(_Args):
     """mirror of struct mphsir_degrade_args"""
     _fields_ = _SZ + [(n, c_void_p) for n in ("clean", "degraded", "clean_aug", "menu", "ksize", "sr_factor", "task", "aug", "param", "sub", "band_sigma",
@@ -310,6 +316,7 @@ _SYMBOLS = {
     "mphsir_scene_fold_d4": (c_int, [ctypes.POINTER(SceneFoldD4Args), c_void_p]),
     "mphsir_quality_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "mphsir_quality": (c_int, [ctypes.POINTER(QualityArgs), c_void_p]),
+    "mphsir_quality_meter": (c_int, [ctypes.POINTER(QualityMeterArgs), c_void_p]),
     "mphsir_degrade_batch": (c_int, [ctypes.POINTER(DegradeArgs), c_void_p]),
     "mphsir_degrade_planes": (c_int, [ctypes.POINTER(DegradeArgs), c_void_p]),
     "mphsir_patch_sample_workspace_bytes": (c_int64, [c_int32, c_int32]),

@@ -812,11 +812,12 @@ def scene_fold_d4(y, store, j0, count, modes):
     return store
 
 
-def quality_bands(restored, clean):
+def quality_bands(restored, clean, out=None):
     """restored, clean (B,C,H,W) fp32 (or (C,H,W): B = 1) -> (psnr (B,C) f64, ssim (B,C) f64, sam_deg (B,) f64, sam_pixels (B,) i64) on
     the inputs' device: band-wise PSNR / SSIM (skimage's, data_range 1) and the mean spectral angle in degrees with the number of pixels
     that have one, both inputs clipped to [0,1], all in float64 (the definitions: include/mphsir.h).  One launch pair on the current
-    stream, no synchronisation, no cube-sized temporary."""
+    stream, no synchronisation, no cube-sized temporary.  out: (psnr, ssim, sam_deg, sam_pixels, workspace) of quality_buffers for these
+    sizes, written in place of fresh tensors (a scoring loop keeps one set)."""
     lib = _lib.load()
     _check(restored, clean)
     assert restored.dtype == clean.dtype == torch.float32, "quality_bands: fp32 inputs, got %s / %s" % (restored.dtype, clean.dtype)
@@ -829,16 +830,58 @@ def quality_bands(restored, clean):
     if nbytes < 0:
         raise RuntimeError("mp-hsir_amd: quality_bands refuses (B %d, C %d, H %d, W %d): H, W >= 7, B, C <= 65535, H * W < 2^31" % (B, C, H, W))
     dev = restored.device
-    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
-    psnr = torch.empty((B, C), dtype=torch.float64, device=dev)
-    ssim = torch.empty((B, C), dtype=torch.float64, device=dev)
-    sam = torch.empty((B,), dtype=torch.float64, device=dev)
-    npix = torch.empty((B,), dtype=torch.int64, device=dev)
+    if out is None:
+        out = quality_buffers(B, C, H, W, dev)
+    psnr, ssim, sam, npix, ws = out
+    _check(*out)
+    assert psnr.dtype == ssim.dtype == sam.dtype == ws.dtype == torch.float64 and npix.dtype == torch.int64 and \
+        tuple(psnr.shape) == tuple(ssim.shape) == (B, C) and tuple(sam.shape) == tuple(npix.shape) == (B,) and ws.numel() * 8 >= nbytes and \
+        all(t.is_contiguous() and t.device == dev for t in out), "quality_bands: out must be quality_buffers(%d, %d, %d, %d, %s)" % (B, C, H, W, dev)
     a = _lib.QualityArgs(restored=_p(restored), clean=_p(clean), psnr=_p(psnr), ssim=_p(ssim), sam_deg=_p(sam), sam_pixels=_p(npix),
                          workspace=_p(ws), workspace_bytes=nbytes, B=B, C=C, H=H, W=W)
     _lib.check(lib.mphsir_quality(ctypes.byref(a), _stream(restored)), "quality")
     _acct("quality", 0.0, 8.0 * restored.numel())
     return psnr, ssim, sam, npix
+
+
+def quality_buffers(B, C, H, W, device):
+    """-> (psnr (B,C) f64, ssim (B,C) f64, sam_deg (B,) f64, sam_pixels (B,) i64, workspace f64): the outputs and the scratch of
+    quality_bands for these sizes, uninitialised"""
+    nbytes = _lib.load().mphsir_quality_workspace_bytes(B, C, H, W)
+    if nbytes < 0:
+        raise RuntimeError("mp-hsir_amd: quality_bands refuses (B %d, C %d, H %d, W %d): H, W >= 7, B, C <= 65535, H * W < 2^31" % (B, C, H, W))
+    return (torch.empty((B, C), dtype=torch.float64, device=device), torch.empty((B, C), dtype=torch.float64, device=device),
+            torch.empty((B,), dtype=torch.float64, device=device), torch.empty((B,), dtype=torch.int64, device=device),
+            torch.empty((nbytes // 8,), dtype=torch.float64, device=device))
+
+
+QUALITY_METER_SLOTS = ("n", "psnr_sum", "ssim_sum", "sam_sum", "nonfinite", "psnr_min", "psnr_max", "skipped")      # a table row (include/mphsir.h)
+
+
+def quality_meter(table, row, psnr, ssim, sam_deg, sam_pixels, use=None, n=None, reset=False):
+    """Adds the images of one scored batch -- psnr, ssim (B,C) f64, sam_deg (B,) f64, sam_pixels (B,) i64 as quality_bands returned them --
+    to row `row` of `table` (S,8) f64 in ONE launch on the current stream: no synchronisation, nothing read back, capturable.  use:
+    (B,C) uint8 / bool, the bands of every image that count (None: all); n: only the first n images count (None: B); reset: the row
+    is initialised first.  The row layout and the per-image rule: include/mphsir.h (QUALITY_METER_SLOTS names the slots).  -> table"""
+    lib = _lib.load()
+    _check(table, psnr, ssim, sam_deg, sam_pixels, use)
+    assert table.dtype == torch.float64 and table.dim() == 2 and table.shape[1] == 8 and table.is_contiguous(), \
+        "quality_meter: table must be a contiguous (S,8) float64 tensor, got %s %s" % (tuple(table.shape), table.dtype)
+    assert psnr.dtype == ssim.dtype == sam_deg.dtype == torch.float64 and sam_pixels.dtype == torch.int64, "quality_meter: float64 psnr / ssim / sam_deg, int64 sam_pixels"
+    assert psnr.dim() == 2 and psnr.shape == ssim.shape and tuple(sam_deg.shape) == tuple(sam_pixels.shape) == (psnr.shape[0],), \
+        "quality_meter: psnr, ssim (B,C) and sam_deg, sam_pixels (B,), got %s %s %s %s" % (tuple(psnr.shape), tuple(ssim.shape), tuple(sam_deg.shape), tuple(sam_pixels.shape))
+    B, C = psnr.shape
+    if use is not None:
+        if use.dtype == torch.bool:
+            use = use.view(torch.uint8)
+        assert use.dtype == torch.uint8 and tuple(use.shape) == (B, C), "quality_meter: use must be (B,C) uint8 or bool, got %s %s" % (tuple(use.shape), use.dtype)
+    ts = (table, psnr, ssim, sam_deg, sam_pixels) + (() if use is None else (use,))
+    assert all(t.is_contiguous() and t.device == table.device for t in ts), "quality_meter: contiguous tensors on one device"
+    a = _lib.QualityMeterArgs(psnr=_p(psnr), ssim=_p(ssim), sam_deg=_p(sam_deg), sam_pixels=_p(sam_pixels), use=_p(use), table=_p(table),
+                              B=B, C=C, n=B if n is None else int(n), rows=table.shape[0], row=int(row), reset=int(bool(reset)))
+    _lib.check(lib.mphsir_quality_meter(ctypes.byref(a), _stream(table)), "quality_meter")
+    _acct("quality_meter", 0.0, 16.0 * B * C + 8.0 * B + 128.0)
+    return table
 
 
 DEG_KINDS = {"none": 0, "gaussianN": 1, "complexN": 2, "blur": 3, "motion_blur": 3, "circle_blur": 3, "sr": 4, "inpaint": 5, "bandmiss": 6,

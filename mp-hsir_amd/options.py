@@ -6,7 +6,8 @@ options.py (options.py:6-37), so its command lines (README.md:36,38) work unchan
 Like the reference, the namespace is built at import time (`from options import options as opt`);
 unknown flags are tolerated so that importing this module under pytest/torchrun does not abort.
 Additions (not present in the reference, all optional): --model, --precision, --steps_per_epoch, --graph,
---synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade, --scene_dir, --crop_jitter, --grad_clip, --ema_decay, --task_classes, --cassi_mask, --cassi_step, --loss_sam, --loss_sdiff.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
+--synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade, --scene_dir, --crop_jitter, --grad_clip, --ema_decay, --task_classes, --cassi_mask, --cassi_step, --loss_sam, --loss_sdiff, --val_dir, --val_every, --val_patch, --val_crops, --val_batch, --val_modes, --val_seed, --val_weights,
+--save_best.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
 into ['0','1'] (options.py:36) and `--classifier type=bool` treats any non-empty string as True.
 --fused_degrade 1 works at every --patch_size: a patch of up to 128 x 128 is degraded by the plane form of the launch, a larger one (256
 out of a --scene_dir store, say) by its tiled form, with the same plan and the same element values.
@@ -71,6 +72,17 @@ _FLAGS = [
     ("--loss_sam", dict(type=float, default=0.0, help="> 0: add this weight times the mean spectral angle (radians) of the restored patch against the "
                         "clean one to the clamp + L1 loss (engine.SpectralLoss, one fused launch pair); 0 (default): off")),
     ("--loss_sdiff", dict(type=float, default=0.0, help="> 0: add this weight times the L1 of the band-to-band differences; 0 (default): off")),
+    # in-training validation (validate.py); --val_every 0 (default): off, the run does what it always did
+    ("--val_dir", dict(type=str, default="", help="directory of held-out .mat / .npy cubes")),
+    ("--val_every", dict(type=int, default=0, help="0 (default): no validation; E: score the held-out set after every E-th epoch and after the last")),
+    ("--val_patch", dict(type=int, default=256, help="side of the crops cut out of the held-out cubes (a multiple of 64)")),
+    ("--val_crops", dict(type=int, default=1, help="crops per cube: 1 (the centre) or k * k (an evenly spread grid)")),
+    ("--val_batch", dict(type=int, default=4, help="crops per validation forward (one degradation mode each)")),
+    ("--val_modes", dict(type=str, default="", help="test.py's modes to score, comma separated (0,5,7,...); default: every mode 0-10 whose prompt id the net has")),
+    ("--val_seed", dict(type=int, default=2025, help="seed of the degraded held-out set")),
+    ("--val_weights", dict(type=str, default="auto", choices=["auto", "ema", "raw"], help="the weights a pass scores: auto = the EMA weights "
+                           "under --ema_decay, else the current ones")),
+    ("--save_best", dict(type=int, default=0, help="1 (with --ckpt_dir): write best.ckpt whenever the mean validation PSNR improves")),
 ]
 
 

@@ -19,6 +19,10 @@ key and shape match, epoch 0); --resume 1 additionally restores the optimizer st
 --loss_sam F / --loss_sdiff F (both 0 by default: the reference's loss) add the mean spectral angle and the L1 of band-to-band
 differences to the loss (engine.SpectralLoss); the log line then ends with the unweighted terms, checkpoints carry the weights as
 `mphsir_loss` and --resume 1 says so when the run's weights differ from the file's.
+--val_every E --val_dir DIR (0 by default: off) scores held-out crops after every E-th epoch and after the last (validate.py: the crops and
+their degraded forms of test.py's modes stay on the device, a pass reads back one small table); rank 0 prints `val epoch E mode M psnr ..
+ssim .. sam .. n ..` per mode and `val epoch E mean ...`, --save_best 1 writes <ckpt_dir>/best.ckpt whenever the mean PSNR improves, and
+checkpoints carry protocol, history and best as `mphsir_val` (--resume 1 restores them, and says so when the protocol differs).
 """
 import os
 import random
@@ -94,15 +98,37 @@ def loss_weights(engine):
     return fn.weights() if isinstance(fn, SpectralLoss) else {"sam": 0.0, "sdiff": 0.0}
 
 
-def save_checkpoint(path, net, engine, epoch):
+def save_checkpoint(path, net, engine, epoch, val=None):
     """Lightning-compatible layout (`state_dict` with the `net.` prefix, `epoch`) + what resuming needs; with EMA weights on,
-    `state_dict_ema` holds them in the same layout (test.py --use_ema 1)."""
+    `state_dict_ema` holds them in the same layout (test.py --use_ema 1).  val: a validate.History -- its protocol, rows and best so
+    far are saved as `mphsir_val` (a run without validation writes the file it always wrote)."""
     ckpt = {"state_dict": {"net." + k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, "epoch": epoch,
             "mphsir_optimizer": engine.optimizer_state(), "mphsir_clip_prompt": net.clip_prompts.detach().cpu().clone(),
             "mphsir_clip_source": net.text_prompt.clip_source, "mphsir_loss": loss_weights(engine)}
     if getattr(engine, "ema_decay", None) is not None:
         ckpt["state_dict_ema"] = {"net." + k: v.detach().cpu().clone() for k, v in engine.ema_state_dict().items()}
+    if val is not None:
+        ckpt["mphsir_val"] = val.state()
     torch.save(ckpt, path)
+
+
+def build_validation(opt, net, eng, data_type, dev):
+    """-> (validate.Validator, validate.History) of --val_dir / --val_*; every refusal ends the run with its message before any training"""
+    from mp_hsir_amd import validate
+    if not opt.val_dir:
+        raise SystemExit("--val_every %d needs --val_dir <directory of held-out .mat / .npy cubes>" % opt.val_every)
+    if opt.val_every < 0:
+        raise SystemExit("--val_every must be >= 0 (0: off)")
+    if opt.val_weights == "ema" and opt.ema_decay <= 0:
+        raise SystemExit("--val_weights ema needs --ema_decay")
+    try:
+        modes = [int(m) for m in opt.val_modes.split(",") if m.strip()] or None
+        vset = validate.ValidationSet(scene_files(opt.val_dir), data_type, dev, modes=modes, patch=opt.val_patch, crops_per_scene=opt.val_crops,
+                                      seed=opt.val_seed, net=net)
+        val = validate.Validator(net, vset, batch=opt.val_batch, engine=eng, weights=opt.val_weights)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    return val, validate.History(vset.protocol(opt.val_weights))
 
 
 def main():
@@ -113,6 +139,8 @@ def main():
         dist.init_process_group("nccl", device_id=dev)
     if rank == 0:
         print("Options\n", opt)
+    if opt.val_every and not opt.val_dir:
+        raise SystemExit("--val_every %d needs --val_dir <directory of held-out .mat / .npy cubes>" % opt.val_every)
     set_seed(opt.seed)
     cfg = dict(MODELS[opt.model or opt.data_type])
     if opt.task_classes:
@@ -132,9 +160,19 @@ def main():
     eng = DataParallelEngine(net, lr=opt.lr, use_graph=bool(opt.graph), grad_clip=opt.grad_clip if opt.grad_clip > 0 else (float("inf") if extras else None),     # EMA alone: measure the norm for the log
                              ema_decay=opt.ema_decay if opt.ema_decay > 0 else None,
                              **(dict(loss_fn=SpectralLoss(opt.loss_sam, opt.loss_sdiff)) if spectral else {}))
+    validator = history = None
+    if opt.val_every:               # 0 (default): nothing of validate.py is imported or built
+        validator, history = build_validation(opt, net, eng, opt.model or opt.data_type, dev)
     start_epoch = 0
     if opt.ckpt_path is not None:
         n, start_epoch = load_warm_start(net, ckpt, dev, eng, resume=bool(opt.resume))
+        if history is not None and opt.resume and ckpt.get("mphsir_val") is not None:
+            note = history.restore(ckpt["mphsir_val"])
+            if rank == 0:
+                print("validation: %d earlier passes restored%s" % (len(history.rows), "" if history.best is None else
+                                                                     ", best mean psnr %.4f at epoch %d" % (history.best["psnr"], history.best["epoch"])), flush=True)
+                if note:
+                    print(note, flush=True)
         if rank == 0:
             print("warm start: %d tensors from %s, %s at epoch %d" % (n, opt.ckpt_path, "resuming" if opt.resume else "starting", start_epoch))
             if not opt.resume and "mphsir_optimizer" in ckpt:
@@ -199,9 +237,17 @@ def main():
                     print("epoch %d it %d lr %.3e grad_norm %.4f clip %.3f train_loss %.5f%s" % (epoch, it + 1, lr, gst["norm"], gst["coef"], running, parts), flush=True)
                 elif rank == 0:
                     print("epoch %d it %d lr %.3e train_loss %.5f%s" % (epoch, it + 1, lr, running, parts), flush=True)
+        if validator is not None and ((epoch + 1) % opt.val_every == 0 or epoch == opt.epochs - 1):
+            result = validator.run()                                  # every rank takes part and gets the same dict
+            if rank == 0:
+                from mp_hsir_amd.validate import result_lines
+                print("\n".join(result_lines(epoch, result)), flush=True)
+                if history.add(epoch, result) and opt.save_best and opt.ckpt_dir:
+                    os.makedirs(opt.ckpt_dir, exist_ok=True)
+                    save_checkpoint(os.path.join(opt.ckpt_dir, "best.ckpt"), net, eng, epoch, val=history)
         if rank == 0 and opt.ckpt_dir and (epoch + 1) % 50 == 0:      # ModelCheckpoint(every_n_epochs=50), train.py:104
             os.makedirs(opt.ckpt_dir, exist_ok=True)
-            save_checkpoint(os.path.join(opt.ckpt_dir, "epoch=%d.ckpt" % epoch), net, eng, epoch)
+            save_checkpoint(os.path.join(opt.ckpt_dir, "epoch=%d.ckpt" % epoch), net, eng, epoch, val=history)
     eng.finish()
     if world > 1:
         dist.destroy_process_group()
