@@ -6,7 +6,7 @@ import torch
 
 import kernel_checks as K
 from guard import guarded
-from kernel_checks import GTOL, TOL, _ROUNDED, _use, inp, rel_l2, rnd
+from kernel_checks import GTOL, TOL, _ROUNDED, _use, close, inp, rel_l2, rnd
 from oracle import mp_hsir_oracle as O
 
 PROLOGUE_CASES = [(64, 2), (128, 4), (128, 2), (256, 8)]
@@ -78,14 +78,16 @@ def check_dsa_prologue(dev, dtype, C, heads, shift, shape=(2, 16, 16)):
     gimg = _from_window_rows(t["gate"].double().cpu()[:, None, :].expand(-1, 64, -1).reshape(M, C), B, H, W, shift)
     img = (t["dt3"].double().cpu() @ t["wsT"].double().cpu().t()).reshape(B, H, W, C) + t["d_out"].double().cpu() * gimg
     want = _to_window_rows(img, shift) + (t["dmu"].double().cpu() / 64.0)[:, None, :].expand(-1, 64, -1).reshape(M, C)
-    e_fused = rel_l2(dsat.reshape(M, C), want)
+    # (both sides back in image order: the same permutation of the rows, so the whole-tensor value is what it was, and the slices are
+    # image rows, image columns and samples)
+    e_fused = close(_from_window_rows(dsat.reshape(M, C).double().cpu(), B, H, W, shift), _from_window_rows(want, B, H, W, shift), TOL[dtype],
+                    geom=(B, H, W), what="dSAt")
     # the three launches it replaces (keep = None: combine_bwd's d_out is its dy, the same d_out as above)
     _, d_sa, _ = ops.combine_bwd(t["d_out"], t["sa"], t["gate"], None, shift)
     d_sa = ops.gemm_tok(t["dt3"], t["wsT"], epi=1, res=d_sa.reshape(M, C)).reshape(B, H, W, C)
     _, _, dsat3, _ = ops.win_attn_bwd(t["x"], d_sa, t["dmu"], *tail)
-    e_three = rel_l2(dsat3.reshape(M, C), want)
+    e_three = rel_l2(_from_window_rows(dsat3.reshape(M, C).double().cpu(), B, H, W, shift), _from_window_rows(want, B, H, W, shift))
     print("dSAt rel-L2 vs fp64: fused %.3e, three launches %.3e (C=%d heads=%d shift=%d %s)" % (e_fused, e_three, C, heads, shift, dtype))
-    assert e_fused < TOL[dtype], (e_fused, TOL[dtype])
     assert e_fused <= e_three, (e_fused, e_three)
     # everything behind the prologue: the plain kernel fed the same rounded total (dmu = 0 adds nothing) returns the same bits
     same = inp(_from_window_rows(dsat.reshape(M, C).cpu(), B, H, W, shift).contiguous())
@@ -204,6 +206,8 @@ def check_block(dev, dtype, name, shift):
         errs[fused] = {k: rel_l2(got[k], want[k]) for k in want}
         bad = {k: v for k, v in errs[fused].items() if not v < (TOL[dtype] * 2 if k == "out" else GTOL[dtype])}
         assert not bad, (name, shift, "fused" if fused else "unfused", bad)
+        for k in want:          # per tensor: no sample, image row, image column or channel of it stands out (2 x 16 x 16: run_block's shape)
+            close(got[k], want[k], TOL[dtype] * 2 if k == "out" else GTOL[dtype], geom=(2, 16, 16), what=k, whole=errs[fused][k])
         errs[fused]["_acct"] = acct
     a1, a0 = errs[True].pop("_acct"), errs[False].pop("_acct")
     assert a1.get("gemm_tok", 0) == a0.get("gemm_tok", 0) - 1, (a1.get("gemm_tok"), a0.get("gemm_tok"))

@@ -474,3 +474,13 @@ def test_guard_was_active():
     after = guard.STATS["kernel_checks"]
     assert after[0] == before[0] + 1 and after[1] >= before[1] + 10, (before, after)
     print("guard: kernel_checks: %d guarded checks, %d guarded allocations so far" % tuple(after[:2]))
+
+
+def test_slice_bounds_were_active():
+    """the checks above compared their tensors through kernel_checks.close (whole-tensor bound AND per-slice bound, tests/slices.py): its
+    counters move; printed per check: the worst slice_err / tol this run saw, of the SLICE_F (or override) it is allowed"""
+    before = list(K.SLICE_STATS.get("check_layernorm_tok", [0, 0.0, ""]))
+    K.check_layernorm_tok("cuda", torch.float32, M=63, C=20)
+    after = K.SLICE_STATS["check_layernorm_tok"]
+    assert after[0] == before[0] + 2 and 0 < after[1] < K.SLICE_F, (before, after)
+    print("\n".join(K.slice_report()))
