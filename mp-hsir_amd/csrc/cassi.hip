@@ -10,7 +10,7 @@
 //                          read neighbouring x of the cube and of the mask.
 //   cassi_emit_kernel      a workgroup owns CE_ROWS OUTPUT rows of one (sample, band) plane: it combines the sample's block pairs (min /
 //                          max are exact and commutative; a NaN pair poisons the result), computes every output pixel at its source
-//                          position under the inverse of the sample's mode (the index map of degrade.hip) and writes whole rows of
+//                          position under the inverse of the sample's mode (D4::source) and writes whole rows of
 //                          `degraded`, and of `clean_aug` when asked, as 16-byte vectors or element by element (uniform per launch).
 //
 // Two launches because the extremes are over the whole measurement of a sample; neither atomics nor a grid-wide wait.  meas holds
@@ -24,8 +24,8 @@
 // All element offsets are 64-bit.
 #include <math.h>
 
-#include "mphsir_dev.h"
 #include "mphsir_host.h"
+#include "mphsir_planar.h"
 
 #pragma clang fp contract(off)
 
@@ -34,8 +34,6 @@ namespace mphsir {
 constexpr int CS_NT = 256;
 constexpr int CS_ROWS = 4;           // measurement rows of a measure workgroup: 512 workgroups at 32 x 64 rows, 256 for one 1024-row scene
 constexpr int CE_ROWS = 32;          // output rows of an emit workgroup
-constexpr unsigned CS_FY = 0xD2u;    // bit m: mode m flips rows    (degrade.hip, scene_d4.hip)
-constexpr unsigned CS_FX = 0xB4u;    // bit m: mode m flips columns
 
 struct CassiDev {
     const float* clean; const float* mask; const int32_t* origin; const int32_t* task; const int32_t* aug;
@@ -48,37 +46,6 @@ struct CassiDev {
 // inlined the pair was fused into one v_fmac (seen in the gfx950 code, and as differing floats with a real-valued mask).
 __device__ __forceinline__ float cs_mul(float a, float b) { return a * b; }
 __device__ __forceinline__ float cs_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float cs_div(float a, float b) {
-#if defined(__HIP__)
-    return __fdiv_rn(a, b);
-#else
-    return a / b;
-#endif
-}
-
-// min, max and NaN flag over the workgroup; valid in every thread after the call
-__device__ __forceinline__ void cs_fold(float& mn, float& mx, float& bad, float (*red)[3]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float o0 = __shfl_xor(mn, m), o1 = __shfl_xor(mx, m), o2 = __shfl_xor(bad, m);
-        mn = o0 < mn ? o0 : mn;
-        mx = o1 > mx ? o1 : mx;
-        bad = o2 > bad ? o2 : bad;
-    }
-    if (lane == 0) {
-        red[wave][0] = mn;
-        red[wave][1] = mx;
-        red[wave][2] = bad;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < CS_NT / 64; ++w) {
-        mn = red[w][0] < mn ? red[w][0] : mn;
-        mx = red[w][1] > mx ? red[w][1] : mx;
-        bad = red[w][2] > bad ? red[w][2] : bad;
-    }
-}
 
 // grid (nblk, B)
 __global__ __launch_bounds__(CS_NT) void cassi_measure_kernel(CassiDev a) {
@@ -114,12 +81,8 @@ __global__ __launch_bounds__(CS_NT) void cassi_measure_kernel(CassiDev a) {
         mx = acc > mx ? acc : mx;
         bad = acc != acc ? 1.f : bad;
     }
-    cs_fold(mn, mx, bad, red);
-    if (t == 0) {
-        float* o = a.part + 2 * ((long)b * a.nblk + blk);
-        o[0] = bad != 0.f ? NAN : mn;
-        o[1] = bad != 0.f ? NAN : mx;
-    }
+    minmax_fold<CS_NT>(mn, mx, bad, red);
+    if (t == 0) minmax_store(a.part + 2 * ((long)b * a.nblk + blk), mn, mx, bad);
 }
 
 // grid (ceil(H / CE_ROWS), C, B)
@@ -128,22 +91,11 @@ __global__ __launch_bounds__(CS_NT) void cassi_emit_kernel(CassiDev a) {
     const int t = threadIdx.x;
     const int c = blockIdx.y, b = blockIdx.z;
     if (a.task && a.task[b] != a.task_id) return;
-    // the sample's extremes from its block pairs; a NaN pair fails both comparisons, so it is flagged on its own
-    float mn = INFINITY, mx = -INFINITY, bad = 0.f;
-    const float* part = a.part + 2 * (long)b * a.nblk;
-    for (int i = t; i < a.nblk; i += CS_NT) {
-        const float v0 = part[2 * i], v1 = part[2 * i + 1];
-        mn = v0 < mn ? v0 : mn;
-        mx = v1 > mx ? v1 : mx;
-        bad = v0 != v0 ? 1.f : bad;
-    }
-    cs_fold(mn, mx, bad, red);
-    const float lo = bad != 0.f ? NAN : mn;
-    const float den = bad != 0.f ? NAN : mx - mn;
+    float lo, den;
+    minmax_combine<CS_NT>(a.part + 2 * (long)b * a.nblk, a.nblk, red, lo, den);      // the sample's extremes from its block pairs
 
     const int H = a.H, W = a.W, Wm = a.Wm;
-    const int m = a.aug ? a.aug[b] & 7 : 0;
-    const bool tr = (m >> 1) & 1, fy = (CS_FY >> m) & 1, fx = (CS_FX >> m) & 1;
+    const D4 d4(a.aug ? a.aug[b] & 7 : 0);
     const long base = ((long)b * a.C + c) * H * W;
     const float* src = a.clean + base;
     const float* meas = a.meas + (long)b * H * Wm + c * a.step;
@@ -152,10 +104,10 @@ __global__ __launch_bounds__(CS_NT) void cassi_emit_kernel(CassiDev a) {
     const int oy0 = blockIdx.x * CE_ROWS, rows = H - oy0 < CE_ROWS ? H - oy0 : CE_ROWS;
     // one output element: its source position under the inverse of the mode
     const auto element = [&](int oy, int ox, float& x) {
-        const int p = tr ? ox : oy, q = tr ? oy : ox;
-        const int sy = fy ? H - 1 - p : p, sx = fx ? W - 1 - q : q;
+        int sy, sx;
+        d4.source(oy, ox, H, W, sy, sx);
         if (oc) x = src[(long)sy * W + sx];
-        return cs_div(meas[(long)sy * Wm + sx] - lo, den);
+        return div_rn(meas[(long)sy * Wm + sx] - lo, den);
     };
     if (a.vec) {                                                  // uniform over the launch
         const int Q = W >> 2;
@@ -216,7 +168,7 @@ extern "C" int mphsir_cassi(const mphsir_cassi_args* a, void* stream) {
                    (long long)a->workspace_bytes, (long long)need);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int nblk = (a->H + CS_ROWS - 1) / CS_ROWS;
-    const bool vec = a->W % 4 == 0 && aligned16(a->degraded) && aligned16(a->clean) && (!a->clean_aug || aligned16(a->clean_aug));
+    const bool vec = rows_aligned16(a->W, a->clean, a->degraded, a->clean_aug);
     float* ws = static_cast<float*>(a->workspace);
     CassiDev d{a->clean, a->mask, a->origin, a->task, a->aug, a->degraded, a->clean_aug, ws, ws + ((int64_t)a->B * a->H * Wm + 3) / 4 * 4,
                a->C, a->H, a->W, (int)Wm, a->MH, a->MW, a->step, a->task_id, nblk, vec ? 1 : 0};

@@ -3,7 +3,7 @@
 //
 // One workgroup of 256 threads owns one (sample, band) plane.  The plane is staged once in LDS -- with a zero halo of k / 2 when the
 // sample is a blur, so that the stencil walk has no bounds test -- and every OUTPUT pixel (oy, ox) is computed from the LDS plane at its
-// source position (sy, sx) under the inverse of the sample's mode (the index map of scene_d4.hip): both outputs leave as whole rows,
+// source position (sy, sx) under the inverse of the sample's mode (D4::source): both outputs leave as whole rows,
 // 256 bytes per wave and store, whatever the mode, and the clean cube is read once.  The kind, the mode and every per-sample parameter
 // are uniform over the workgroup: scalar loads and scalar branches.
 //
@@ -33,8 +33,8 @@
 // so no value depends on the tile grid.  W % 4 == 0 and 16-byte aligned cubes (an instance of their own, VEC): the tile is staged with
 // dwordx4 loads and both outputs leave as dwordx4 stores (a stencil's under the modes that do not transpose).  Bound by HBM for every kind but the large stencils
 // (441 fmas per output: the vector ALU) and gaussianN / complexN with generated draws (ten Philox rounds, log, cos: the vector ALU).
-#include "mphsir_dev.h"
 #include "mphsir_host.h"
+#include "mphsir_planar.h"
 #include <type_traits>
 
 #pragma clang fp contract(off)
@@ -43,8 +43,6 @@ namespace mphsir {
 
 constexpr int DG_NT = 256;
 constexpr int DG_SS = MPHSIR_DEG_STENCIL_SIDE;
-constexpr unsigned D4Q_FY = 0xD2u;   // bit m: mode m flips rows    (scene_d4.hip)
-constexpr unsigned D4Q_FX = 0xB4u;   // bit m: mode m flips columns
 
 struct DegradeDev {
     const float* clean; float* degraded; float* clean_aug;
@@ -217,8 +215,8 @@ template <bool GEN> __global__ __launch_bounds__(DG_NT) void degrade_batch_kerne
     const long base = (long)bc * N * N;
     const float* src = a.clean + base;
     const int kind = a.menu[dg_clamp(a.task[b], a.T)];
-    const int m = a.aug[b] & 7;
-    const bool tr = (m >> 1) & 1, fy = (D4Q_FY >> m) & 1, fx = (D4Q_FX >> m) & 1;
+    const D4 d4(a.aug[b] & 7);
+    const bool tr = d4.tr, fy = d4.fy, fx = d4.fx;
     const int sub = a.sub ? a.sub[b] : 0;
     const float par = a.param ? a.param[b] : 0.f;
 
@@ -292,8 +290,8 @@ template <bool GEN> __global__ __launch_bounds__(DG_NT) void degrade_batch_kerne
 
     for (int oy = tid >> 6; oy < N; oy += DG_NT / 64) {
         for (int ox = tid & 63; ox < N; ox += 64) {
-            const int p = tr ? ox : oy, q = tr ? oy : ox;
-            const int sy = fy ? N - 1 - p : p, sx = fx ? N - 1 - q : q;
+            int sy, sx;
+            d4.source(oy, ox, N, N, sy, sx);
             const float x = lds[(sy + h) * pitch + sx + h];
             const int el = sy * N + sx;
             float z = 0.f, u0 = 0.f, u1 = 0.f;
@@ -319,8 +317,8 @@ template <bool GEN, bool VEC> __global__ __launch_bounds__(DG_NT) void degrade_p
     const long base = (long)bc * H * W;
     const float* src = a.clean + base;
     const int kind = a.menu[dg_clamp(a.task[b], a.T)];
-    const int m = a.aug ? a.aug[b] & 7 : 0;
-    const bool tr = (m >> 1) & 1, fy = (D4Q_FY >> m) & 1, fx = (D4Q_FX >> m) & 1;
+    const D4 d4(a.aug ? a.aug[b] & 7 : 0);
+    const bool tr = d4.tr, fy = d4.fy, fx = d4.fx;
     const int sub = a.sub ? a.sub[b] : 0;
     const float par = a.param ? a.param[b] : 0.f;
 
@@ -444,8 +442,8 @@ template <bool GEN, bool VEC> __global__ __launch_bounds__(DG_NT) void degrade_p
         // the kinds of this loop, for the compiler to see (the subtype of complexN is folded into t.bflag above)
         const int kd = !DRAWS ? kind : kind == MPHSIR_DEG_COMPLEX ? MPHSIR_DEG_COMPLEX : kind == MPHSIR_DEG_INPAINT ? MPHSIR_DEG_INPAINT : MPHSIR_DEG_GAUSSIAN;
         const auto element = [&](int oy, int ox, float& x) {
-            const int p = tr ? ox : oy, q = tr ? oy : ox;
-            const int sy = fy ? H - 1 - p : p, sx = fx ? W - 1 - q : q;
+            int sy, sx;
+            d4.source(oy, ox, H, W, sy, sx);
             x = xl[sy * (DG_T | 1) + sx];
             const int el = sy * W + sx;
             float z = 0.f, u0 = 0.f, u1 = 0.f;
@@ -610,8 +608,7 @@ extern "C" int mphsir_degrade_planes(const mphsir_degrade_args* a, void* stream)
     const long blocks = (long)a->B * a->C * d.ntx * d.nty;
     MPHSIR_REQUIRE(blocks < (1L << 31), "degrade_planes: %ld tiles (B %d, C %d, %d x %d tiles of %d x %d): 2^31 or more", blocks, a->B, a->C, d.nty, d.ntx, DG_T,
                    DG_T);
-    const auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-    const bool vec = a->W % 4 == 0 && a16(a->clean) && a16(a->degraded) && a16(a->clean_aug);
+    const bool vec = rows_aligned16(a->W, a->clean, a->degraded, a->clean_aug);
     long low_off = 0;
     const size_t shmem = (size_t)degrade_planes_lds_floats(hmax, a->sr_factor, (kinds >> MPHSIR_DEG_SR) & 1u ? a->F : 0, (kinds >> MPHSIR_DEG_BLUR) & 1u, &low_off) * sizeof(float);
     d.low_off = (int)low_off;

@@ -61,6 +61,8 @@ bool diag_skip(int kid);
 inline int dtype_size(int dt) { return dt == MPHSIR_F32 ? 4 : 2; }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// the 16-byte path of a planar kernel: every row of every cube starts on 16 bytes (a cube that is not given, NULL, is aligned)
+inline bool rows_aligned16(int W, const void* a, const void* b, const void* c) { return W % 4 == 0 && aligned16(a) && aligned16(b) && aligned16(c); }
 
 // dynamic LDS above 64 KiB must be opted into per kernel function; done once per (function, size) so that replays /
 // stream captures of a warmed-up step issue no runtime-attribute calls

@@ -9,8 +9,8 @@
 // Further down, off unless the caller asks (engine.DataParallelEngine(grad_clip=, ema_decay=)): the global gradient norm in float64
 // (grad_sqnorm_kernel + grad_norm_finish_kernel) and flat_adamw_ex_kernel, the same AdamW pass with the clip factor on the gradient and
 // an EMA arena updated from the parameter it has just formed (5 reads + 4 writes then).
-#include "mphsir_dev.h"
 #include "mphsir_host.h"
+#include "mphsir_planar.h"
 
 namespace mphsir {
 
@@ -91,18 +91,12 @@ __global__ void scaler_update_kernel(float* scaler, float growth, float backoff,
 // the host verified that the workspace holds nblk doubles; the finish reads partials i < nblk only.
 constexpr int GN_MAX_BLOCKS = 256 * 8;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 // the block's total in thread 0 (every thread of the block must call)
 __device__ __forceinline__ double block_sum_f64(double v, double* red) {
-    v = wave_sum_f64(v);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
+    return sum4_ordered(red, 1);
 }
 
 __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const float* __restrict__ g, long n, double* __restrict__ part) {
@@ -132,7 +126,7 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(GradNormFinishDev
     if (threadIdx.x != 0) return;
     const double norm = sqrt(S) * (double)a.grad_scale / (a.scaler ? (double)a.scaler[0] : 1.0);
     a.stats[0] = (float)norm;
-    if (fabs(norm) <= 1.7976931348623157e308) {           // false for inf and for NaN
+    if (finite(norm)) {
         const double c = (double)a.max_norm / (norm + 1e-6);
         a.stats[1] = (float)(c < 1.0 ? c : 1.0);
         a.stats[3] = 0.f;

@@ -23,8 +23,8 @@
 // element (b, c, r, x) inside [B][C][P][P].
 #include <math.h>
 
-#include "mphsir_dev.h"
 #include "mphsir_host.h"
+#include "mphsir_planar.h"
 
 namespace mphsir {
 
@@ -36,14 +36,6 @@ struct PatchDev {
     const float* arena; const int64_t* levels; const int32_t* records; const int64_t* index; float* out; float* ws;
     int n_levels, n_records, C, P;
 };
-
-__device__ __forceinline__ float ps_div(float a, float b) {
-#if defined(__HIP__)
-    return __fdiv_rn(a, b);          // correctly rounded whatever the fast-math flags of the build
-#else
-    return a / b;
-#endif
-}
 
 // the window of sample b, band c: pointer to its first element and the level's row pitch
 __device__ __forceinline__ const float* ps_plane(const PatchDev& a, int b, int c, int& W) {
@@ -62,15 +54,10 @@ __device__ __forceinline__ const float* ps_plane(const PatchDev& a, int b, int c
     return a.arena + off + ((long)c * H + y) * (long)W + x;
 }
 
-__device__ __forceinline__ f32x4 ps_load(const float* p, bool vec) {
-    if (vec) return *reinterpret_cast<const f32x4*>(p);
-    return f32x4{p[0], p[1], p[2], p[3]};
-}
-
 // grid (C, B)
 __global__ __launch_bounds__(PS_NT) void patch_minmax_kernel(PatchDev a) {
     __shared__ float red[PS_NT / 64][3];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int c = blockIdx.x, b = blockIdx.y;
     int W;
     const float* src = ps_plane(a, b, c, W);
@@ -82,7 +69,7 @@ __global__ __launch_bounds__(PS_NT) void patch_minmax_kernel(PatchDev a) {
 #pragma unroll
         for (int u = 0; u < PS_U; ++u) {                  // all loads of the round first: PS_U independent 16-byte requests in flight
             const int q = q0 + u * PS_NT, r = q / p4, x = (q - r * p4) * 4;
-            if (q < quads) v[u] = ps_load(src + (long)r * W + x, vec);
+            if (q < quads) v[u] = load4_if(src + (long)r * W + x, vec, 4);
         }
 #pragma unroll
         for (int u = 0; u < PS_U; ++u) {
@@ -96,67 +83,17 @@ __global__ __launch_bounds__(PS_NT) void patch_minmax_kernel(PatchDev a) {
             }
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float o0 = __shfl_xor(mn, m), o1 = __shfl_xor(mx, m), o2 = __shfl_xor(bad, m);
-        mn = o0 < mn ? o0 : mn;
-        mx = o1 > mx ? o1 : mx;
-        bad = o2 > bad ? o2 : bad;
-    }
-    if (lane == 0) {
-        red[wave][0] = mn;
-        red[wave][1] = mx;
-        red[wave][2] = bad;
-    }
-    __syncthreads();
-    if (t == 0) {
-#pragma unroll
-        for (int w = 1; w < PS_NT / 64; ++w) {
-            mn = red[w][0] < mn ? red[w][0] : mn;
-            mx = red[w][1] > mx ? red[w][1] : mx;
-            bad = red[w][2] > bad ? red[w][2] : bad;
-        }
-        float* o = a.ws + 2 * ((long)b * a.C + c);
-        o[0] = bad != 0.f ? NAN : mn;
-        o[1] = bad != 0.f ? NAN : mx;
-    }
+    minmax_fold<PS_NT>(mn, mx, bad, red);
+    if (t == 0) minmax_store(a.ws + 2 * ((long)b * a.C + c), mn, mx, bad);
 }
 
 // grid (C, B)
 __global__ __launch_bounds__(PS_NT) void patch_normalise_kernel(PatchDev a) {
     __shared__ float red[PS_NT / 64][3];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int c = blockIdx.x, b = blockIdx.y;
-    // the sample's extremes from its C plane pairs; a NaN pair fails both comparisons, so it is flagged on its own
-    float mn = INFINITY, mx = -INFINITY, bad = 0.f;
-    const float* part = a.ws + 2 * (long)b * a.C;
-    for (int i = t; i < a.C; i += PS_NT) {
-        const float v0 = part[2 * i], v1 = part[2 * i + 1];
-        mn = v0 < mn ? v0 : mn;
-        mx = v1 > mx ? v1 : mx;
-        bad = v0 != v0 ? 1.f : bad;
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float o0 = __shfl_xor(mn, m), o1 = __shfl_xor(mx, m), o2 = __shfl_xor(bad, m);
-        mn = o0 < mn ? o0 : mn;
-        mx = o1 > mx ? o1 : mx;
-        bad = o2 > bad ? o2 : bad;
-    }
-    if (lane == 0) {
-        red[wave][0] = mn;
-        red[wave][1] = mx;
-        red[wave][2] = bad;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < PS_NT / 64; ++w) {
-        mn = red[w][0] < mn ? red[w][0] : mn;
-        mx = red[w][1] > mx ? red[w][1] : mx;
-        bad = red[w][2] > bad ? red[w][2] : bad;
-    }
-    const float lo = bad != 0.f ? NAN : mn;
-    const float den = bad != 0.f ? NAN : mx - mn;
+    float lo, den;
+    minmax_combine<PS_NT>(a.ws + 2 * (long)b * a.C, a.C, red, lo, den);      // the sample's extremes from its C plane pairs
 
     int W;
     const float* src = ps_plane(a, b, c, W);
@@ -168,7 +105,7 @@ __global__ __launch_bounds__(PS_NT) void patch_normalise_kernel(PatchDev a) {
 #pragma unroll
         for (int u = 0; u < PS_U; ++u) {
             const int q = q0 + u * PS_NT, r = q / p4, x = (q - r * p4) * 4;
-            if (q < quads) v[u] = ps_load(src + (long)r * W + x, vec);
+            if (q < quads) v[u] = load4_if(src + (long)r * W + x, vec, 4);
         }
 #pragma unroll
         for (int u = 0; u < PS_U; ++u) {
@@ -176,7 +113,7 @@ __global__ __launch_bounds__(PS_NT) void patch_normalise_kernel(PatchDev a) {
             if (q < quads) {
                 f32x4 o;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) o[k] = ps_div(v[u][k] - lo, den);
+                for (int k = 0; k < 4; ++k) o[k] = div_rn(v[u][k] - lo, den);
                 *reinterpret_cast<f32x4*>(dst + 4 * (long)q) = o;
             }
         }

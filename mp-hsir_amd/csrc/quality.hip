@@ -21,8 +21,8 @@
 // enter window sums that are never used); workspace slot (b, c, block) lies inside the 16 (C+1) blocks B bytes the host verified.
 #include <math.h>
 
-#include "mphsir_dev.h"
 #include "mphsir_host.h"
+#include "mphsir_planar.h"
 
 namespace mphsir {
 
@@ -39,17 +39,6 @@ struct QualityDev {
     const float* x; const float* y; double* ws;
     int C, H, W, tiles_x, nblk;
 };
-
-// comparisons, not fminf / fmaxf: a NaN stays a NaN
-__device__ __forceinline__ float clip01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
-__device__ __forceinline__ double floor0(double v) { return v < 0.0 ? 0.0 : v; }
-
-// sum over the wave in a fixed tree; every lane ends with the total
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
 
 // grid (blocks per image, B)
 __global__ __launch_bounds__(Q_NT) void quality_partials_kernel(QualityDev a) {
@@ -98,8 +87,8 @@ __global__ __launch_bounds__(Q_NT) void quality_partials_kernel(QualityDev a) {
         for (int k = 0; k < Q_LD; ++k) {
             const int e = t + k * Q_NT;
             if (e < Q_SW * Q_SH) {
-                bxs[e] = clip01(rx[k]);
-                bys[e] = clip01(ry[k]);
+                bxs[e] = clamp01(rx[k]);
+                bys[e] = clamp01(ry[k]);
             }
         }
         if (c + 1 < a.C) {
@@ -114,8 +103,8 @@ __global__ __launch_bounds__(Q_NT) void quality_partials_kernel(QualityDev a) {
         __syncthreads();                     // the stage of band c is complete; everyone is done with hs and red of band c - 1
         if (t == 0 && c > 0) {
             double* o = ws + (long)(c - 1) * a.nblk * 2;
-            o[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-            o[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+            o[0] = sum4_ordered(&red[0][0], 2);
+            o[1] = sum4_ordered(&red[0][1], 2);
         }
         // row sums: staged row r, the windows centred on tile columns col and col + 1 share six of their seven samples
         for (int e = t; e < Q_SH * (Q_TW / 2); e += Q_NT) {
@@ -200,11 +189,11 @@ __global__ __launch_bounds__(Q_NT) void quality_partials_kernel(QualityDev a) {
     __syncthreads();
     if (t == 0) {
         double* o = ws + (long)(a.C - 1) * a.nblk * 2;
-        o[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-        o[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+        o[0] = sum4_ordered(&red[0][0], 2);
+        o[1] = sum4_ordered(&red[0][1], 2);
         o += (long)a.nblk * 2;
-        o[0] = ((red_sam[0][0] + red_sam[1][0]) + red_sam[2][0]) + red_sam[3][0];
-        o[1] = ((red_sam[0][1] + red_sam[1][1]) + red_sam[2][1]) + red_sam[3][1];
+        o[0] = sum4_ordered(&red_sam[0][0], 2);
+        o[1] = sum4_ordered(&red_sam[0][1], 2);
     }
 }
 

@@ -13,8 +13,8 @@
 //
 // Bounds: image b < n <= B and band c < C index psnr / ssim / use at b * C + c < B * C, sam_deg at b < B; the row lies at
 // row * 8 .. row * 8 + 7 with 0 <= row < rows (all verified by the host before the launch); LDS slots are indexed by threadIdx.x < QM_NT.
-#include "mphsir_dev.h"
 #include "mphsir_host.h"
+#include "mphsir_planar.h"
 
 // sums and one divide: nothing here may be fused or reassociated, the table is compared bitwise with a float64 restatement
 #pragma clang fp contract(off)
@@ -28,9 +28,6 @@ struct QualityMeterDev {
     const double* psnr; const double* ssim; const double* sam; const uint8_t* use; double* row;
     int C, n, reset;
 };
-
-// v - v is 0 for every finite v and NaN for +-inf and NaN (no reliance on a classification builtin under any math flag)
-__device__ __forceinline__ bool finite64(double v) { return v - v == 0.0; }
 
 __global__ __launch_bounds__(QM_NT) void quality_meter_kernel(QualityMeterDev a) {
     __shared__ double sp[QM_NT], ss[QM_NT], sa[QM_NT];
@@ -66,7 +63,7 @@ __global__ __launch_bounds__(QM_NT) void quality_meter_kernel(QualityMeterDev a)
             if (cnt > 0) {
                 ap = ap / (double)cnt;
                 as = as / (double)cnt;
-                k = finite64(ap) && finite64(as) && finite64(sam) ? QM_SCORED : QM_NONFINITE;
+                k = finite(ap) && finite(as) && finite(sam) ? QM_SCORED : QM_NONFINITE;
             }
             sp[t] = ap;
             ss[t] = as;

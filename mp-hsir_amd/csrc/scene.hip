@@ -15,22 +15,12 @@
 // dereferences tile (iy,ix) only at local coordinates it has checked against [0,th) x [0,tw) (the pointer `src` itself may be formed
 // up to 3 floats outside a row and is then never read through).  Origins are expected within +-2^30, so that origin + coordinate
 // stays inside int; the host cannot check device arrays, and beyond that range the sums wrap before they are folded / compared.
-#include "mphsir_dev.h"
 #include "mphsir_host.h"
+#include "mphsir_planar.h"
 
 namespace mphsir {
 
 constexpr int SCENE_CH = 8;        // channels per thread
-
-// torch's `reflect` for any integer coordinate (period 2(n-1)); n == 1 maps everything to 0
-__device__ __forceinline__ int mirror(int y, int n) {
-    if ((unsigned)y < (unsigned)n) return y;
-    const int p = 2 * (n - 1);
-    if (p == 0) return 0;
-    int m = y % p;
-    m = m < 0 ? m + p : m;
-    return m < n ? m : p - m;
-}
 
 struct GatherDev {
     const float* scene; const int* origins; float* tiles;

@@ -5,13 +5,8 @@
 //   d4_gather   tiles [count][C][th][tw] <- mode_g(mirror-cut tile t of scene [C][H][W]) for the items j = g * n_tiles + t of a batch
 //   d4_fold     store [n_tiles][C][th][tw] <- (store or 0) + sum over the batch's items of a tile, in ascending j, of inverse_mode_g(y)
 //
-// Every mode is one index map: element (u, v) of the transformed tile is element (a, b) of the tile with
-//       (p, q) = transposing ? (v, u) : (u, v),   a = fy ? rows - 1 - p : p,   b = fx ? cols - 1 - q : q
-//   mode        0  1  2  3  4  5  6  7
-//   transposing .  .  x  x  .  .  x  x      (m >> 1) & 1; th == tw
-//   fy          .  x  .  .  x  .  x  x      D4_FY
-//   fx          .  .  x  .  x  x  .  x      D4_FX
-// and the fold reads y through the same map the other way round.
+// Every mode is one index map of the tile (struct D4 of mphsir_planar.h holds the table; a transposing mode has th == tw), and the fold
+// reads y through the same map the other way round.
 //
 // Both are streaming kernels; a thread owns 4 consecutive x of one row of the TILE side and walks a chunk of channels, as in scene.hip.
 // Non-transposing modes: the tile side moves as 16-byte vectors; a reversed row is the quad at the mirrored column, reversed in
@@ -25,8 +20,8 @@
 //
 // The modes come by value and the item arithmetic uses validated scalars only; the one device array, `origins`, is read at t < n_tiles
 // and its values are folded into the scene by the mirror map, so no access depends on it holding a valid plan (origins within +-2^30).
-#include "mphsir_dev.h"
 #include "mphsir_host.h"
+#include "mphsir_planar.h"
 
 namespace mphsir {
 
@@ -35,18 +30,6 @@ constexpr int D4_LC = 4;             // channels per pass through LDS (4 * 32 * 
                                      // thread of the fold, whose accumulators and loads in flight are 8 registers a channel
 constexpr int D4_S = 32;             // side of a workgroup's square in the transposing modes
 constexpr int D4_P = D4_S + 1;       // LDS row pitch in dwords
-constexpr unsigned D4_FY = 0xD2u;    // bit m: mode m flips rows    (1, 4, 6, 7)
-constexpr unsigned D4_FX = 0xB4u;    // bit m: mode m flips columns (2, 4, 5, 7)
-
-// torch's `reflect` for any integer coordinate, as in scene.hip
-__device__ __forceinline__ int d4_mirror(int y, int n) {
-    if ((unsigned)y < (unsigned)n) return y;
-    const int p = 2 * (n - 1);
-    if (p == 0) return 0;
-    int m = y % p;
-    m = m < 0 ? m + p : m;
-    return m < n ? m : p - m;
-}
 
 struct D4GatherDev {
     const float* scene; const int* origins; float* tiles;
@@ -58,23 +41,23 @@ __global__ __launch_bounds__(256) void d4_gather_kernel(D4GatherDev a) {
     __shared__ float lds[D4_LC][D4_S][D4_P];
     const int jz = a.j0 + (int)blockIdx.z, j = jz < a.last ? jz : a.last;
     const int g = j / a.n_tiles, t = j - g * a.n_tiles;
-    const int m = (a.modes >> (3 * g)) & 7;
-    const bool fy = (D4_FY >> m) & 1, fx = (D4_FX >> m) & 1;
+    const D4 d4((a.modes >> (3 * g)) & 7);
+    const bool fy = d4.fy, fx = d4.fx;
     const int oy = a.origins[2 * t], ox = a.origins[2 * t + 1];
     const int c0 = blockIdx.y * D4_CH;
     const long plane = (long)a.H * a.W, tplane = (long)a.th * a.tw;
     const float* src = a.scene + c0 * plane;
     float* dst = a.tiles + ((long)blockIdx.z * a.C + c0) * tplane;
     const int tid = threadIdx.x;
-    if (!(m & 2)) {
+    if (!d4.tr) {
         const int tw4 = a.tw >> 2;
         const int idx = blockIdx.x * 256 + tid;
         if (idx >= a.th * tw4) return;
         const int u = idx / tw4, v = (idx - u * tw4) * 4;
-        const long row = (long)d4_mirror(oy + (fy ? a.th - 1 - u : u), a.H) * a.W;
+        const long row = (long)mirror(oy + (fy ? a.th - 1 - u : u), a.H) * a.W;
         int x[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] = d4_mirror(ox + (fx ? a.tw - 1 - (v + k) : v + k), a.W);
+        for (int k = 0; k < 4; ++k) x[k] = mirror(ox + (fx ? a.tw - 1 - (v + k) : v + k), a.W);
         src += row;
         dst += (long)u * a.tw + v;
 #pragma unroll
@@ -94,12 +77,12 @@ __global__ __launch_bounds__(256) void d4_gather_kernel(D4GatherDev a) {
     const int U0 = ((int)blockIdx.x / nb) * D4_S, V0 = ((int)blockIdx.x % nb) * D4_S;
     const int lq = tid & 31, lp0 = tid >> 5;                      // loader: column q = U0 + lq of P, rows p = V0 + lp0 + 8k
     const int q = U0 + lq;
-    const int col = d4_mirror(ox + (fx ? n - 1 - q : q), a.W);
+    const int col = mirror(ox + (fx ? n - 1 - q : q), a.W);
     long rows[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int p = V0 + lp0 + 8 * k;
-        rows[k] = (long)d4_mirror(oy + (fy ? n - 1 - p : p), a.H) * a.W;      // p >= n: a legal address whose value is never stored
+        rows[k] = (long)mirror(oy + (fy ? n - 1 - p : p), a.H) * a.W;      // p >= n: a legal address whose value is never stored
     }
     const int ou = tid >> 3, ov = (tid & 7) * 4;                  // writer: row U0 + ou, columns V0 + ov .. + 3
     const bool wr = U0 + ou < n && V0 + ov < n;
@@ -169,10 +152,10 @@ __global__ __launch_bounds__(256) void d4_fold_kernel(D4FoldDev a) {
 #pragma unroll 1
     for (int r = 0; r < items; ++r) {
         const int g = gf + r;
-        const int m = (a.modes >> (3 * g)) & 7;
-        const bool fy = (D4_FY >> m) & 1, fx = (D4_FX >> m) & 1;
+        const D4 d4((a.modes >> (3 * g)) & 7);
+        const bool fy = d4.fy, fx = d4.fx;
         const float* y = a.y + ((long)((int)blockIdx.z + r * a.n_tiles) * a.C + c0) * tplane;
-        if (!(m & 2)) {
+        if (!d4.tr) {
             if (own) {
                 const float* s = y + (long)(fy ? a.th - 1 - ra : ra) * a.tw + (fx ? a.tw - 4 - rb : rb);
 #pragma unroll
@@ -184,7 +167,7 @@ __global__ __launch_bounds__(256) void d4_fold_kernel(D4FoldDev a) {
                     }
                 }
             }
-            continue;          // m belongs to the item, so it is uniform over the workgroup: all of it skips the barriers below, or none
+            continue;          // the mode belongs to the item, so it is uniform over the workgroup: all of it skips the barriers below, or none
         }
         // transposing (square, th == tw == n): store (a, b) takes y (u, v) = (fx ? n - 1 - b : b, fy ? n - 1 - a : a)
         const int n = a.th;

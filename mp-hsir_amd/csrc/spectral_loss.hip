@@ -24,8 +24,8 @@
 // 24 * B * blocks bytes the host verified.
 #include <math.h>
 
-#include "mphsir_dev.h"
 #include "mphsir_host.h"
+#include "mphsir_planar.h"
 
 // No multiply-add is fused in this file: whether a*b + c becomes one rounding or two would otherwise be the compiler's choice per
 // instantiation, and the 16-byte path and the scalar path (and the CPU build the tests run) would differ in their last bits.
@@ -46,42 +46,12 @@ struct SpectralLossDev {
     float inv_n, inv_sd;        // 1 / (B C H W), w_sdiff / (B (C - 1) H W)
 };
 
-// comparisons, not fminf / fmaxf: a NaN stays a NaN (mphsir_l1_clamp_loss's clamp)
-__device__ __forceinline__ float sl_clamp01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
-__device__ __forceinline__ f32x4 sl_clamp01(f32x4 v) { return f32x4{sl_clamp01(v[0]), sl_clamp01(v[1]), sl_clamp01(v[2]), sl_clamp01(v[3])}; }
-__device__ __forceinline__ double sl_floor0(double v) { return v < 0.0 ? 0.0 : v; }
-__device__ __forceinline__ bool sl_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }      // false for a NaN
 __device__ __forceinline__ float sl_sign(double v) { return v > 0.0 ? 1.f : (v < 0.0 ? -1.f : 0.f); }
 // e = (x1 - x0) - (c1 - c0) in float64: the one expression both walks (and both waves that need an e at a quarter's edge) evaluate
 __device__ __forceinline__ double sl_e(float x1, float x0, float c1, float c0) { return ((double)x1 - (double)x0) - ((double)c1 - (double)c0); }
 
 // plane index of band k for a load that runs ahead of the walk: past the last band it repeats the last (in bounds, never used)
 __device__ __forceinline__ long sl_band(int k, int C) { return k < C ? k : C - 1; }
-
-// sum over the wave in a fixed tree; every lane ends with the total
-__device__ __forceinline__ double sl_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
-// four neighbouring pixels of one plane; nv of them exist
-template <bool VEC> __device__ __forceinline__ f32x4 sl_load(const float* p, int nv) {
-    if (VEC) return nv ? *reinterpret_cast<const f32x4*>(p) : f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = j < nv ? p[j] : 0.f;
-    return v;
-}
-template <bool VEC> __device__ __forceinline__ void sl_store(float* p, f32x4 v, int nv) {
-    if (VEC) {
-        if (nv) *reinterpret_cast<f32x4*>(p) = v;
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (j < nv) p[j] = v[j];
-}
 
 // grid (B * nbi): workgroup blk owns pixels [(blk % nbi) * SL_PIX, + SL_PIX) of image blk / nbi
 template <bool VEC> __global__ __launch_bounds__(SL_NT) void spectral_loss_kernel(SpectralLossDev a) {
@@ -107,10 +77,10 @@ template <bool VEC> __global__ __launch_bounds__(SL_NT) void spectral_loss_kerne
         // Two bands ahead of the arithmetic, without a branch around the loads (the band index is clamped to the image's last plane, a
         // repeated plane is never used): the chain of dependent loads is half as long as the quarter.  Band k + 1 is the next of this
         // quarter or -- for e_k alone -- the first of the next wave's.
-        f32x4 x = sl_clamp01(sl_load<VEC>(py + sl_band(k0, C) * a.plane, nv)), c = sl_load<VEC>(pc + sl_band(k0, C) * a.plane, nv);
-        f32x4 xn = sl_clamp01(sl_load<VEC>(py + sl_band(k0 + 1, C) * a.plane, nv)), cn = sl_load<VEC>(pc + sl_band(k0 + 1, C) * a.plane, nv);
+        f32x4 x = clamp01(load4_if(py + sl_band(k0, C) * a.plane, VEC, nv)), c = load4_if(pc + sl_band(k0, C) * a.plane, VEC, nv);
+        f32x4 xn = clamp01(load4_if(py + sl_band(k0 + 1, C) * a.plane, VEC, nv)), cn = load4_if(pc + sl_band(k0 + 1, C) * a.plane, VEC, nv);
         for (int k = k0; k < k1; ++k) {
-            const f32x4 x2 = sl_clamp01(sl_load<VEC>(py + sl_band(k + 2, C) * a.plane, nv)), c2 = sl_load<VEC>(pc + sl_band(k + 2, C) * a.plane, nv);
+            const f32x4 x2 = clamp01(load4_if(py + sl_band(k + 2, C) * a.plane, VEC, nv)), c2 = load4_if(pc + sl_band(k + 2, C) * a.plane, VEC, nv);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const double xv = x[j], cv = c[j], d = xv - cv;
@@ -137,8 +107,8 @@ template <bool VEC> __global__ __launch_bounds__(SL_NT) void spectral_loss_kerne
             st[wave][2][j][lane] = sdd[j];
         }
     }
-    l1 = sl_wave_sum(l1);
-    sd = sl_wave_sum(sd);
+    l1 = wave_sum(l1);
+    sd = wave_sum(sd);
     if (lane == 0) {
         red[wave][0] = l1;
         red[wave][1] = sd;
@@ -153,46 +123,45 @@ template <bool VEC> __global__ __launch_bounds__(SL_NT) void spectral_loss_kerne
     if (a.do_sam) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const double X = ((st[0][0][j][lane] + st[1][0][j][lane]) + st[2][0][j][lane]) + st[3][0][j][lane];
-            const double Cc = ((st[0][1][j][lane] + st[1][1][j][lane]) + st[2][1][j][lane]) + st[3][1][j][lane];
-            const double D = ((st[0][2][j][lane] + st[1][2][j][lane]) + st[2][2][j][lane]) + st[3][2][j][lane];
+            const double X = sum4_ordered(&st[0][0][j][lane], 3 * 4 * 64), Cc = sum4_ordered(&st[0][1][j][lane], 3 * 4 * 64);
+            const double D = sum4_ordered(&st[0][2][j][lane], 3 * 4 * 64);
             const double nx = sqrt(X), ny = sqrt(Cc);
             const bool has = nx != 0.0 && ny != 0.0;                         // true for a NaN: the loss becomes NaN
             const double dm = nx - ny, sp = nx + ny;
-            const double s2 = sl_floor0(D - dm * dm), t2 = sl_floor0(sp * sp - D), h2 = s2 + t2;
+            const double s2 = floor0(D - dm * dm), t2 = floor0(sp * sp - D), h2 = s2 + t2;
             if (wave == 0 && has) th += 2.0 * atan2(sqrt(s2), sqrt(t2));
             const double sn = 2.0 * sqrt(s2 * t2) / h2, cs = (t2 - s2) / h2;  // sin, cos of theta = 2 atan2(sqrt s2, sqrt t2)
-            if (has && sl_finite(X) && sl_finite(Cc) && sl_finite(D) && sn >= MPHSIR_SAM_MIN_SIN) {
+            if (has && finite(X) && finite(Cc) && finite(D) && sn >= MPHSIR_SAM_MIN_SIN) {
                 af[j] = (float)(a.sam_scale / (sn * nx * ny));
                 bf[j] = (float)(a.sam_scale * cs / (sn * X));
             }
         }
     }
     if (wave == 0) {
-        th = sl_wave_sum(th);
+        th = wave_sum(th);
         if (lane == 0) {
             double* o = a.ws + 3 * (long)blockIdx.x;
-            o[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+            o[0] = sum4_ordered(&red[0][0], 2);
             o[1] = th;
-            o[2] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+            o[2] = sum4_ordered(&red[0][1], 2);
         }
     }
     if (a.g == nullptr || k0 >= k1) return;
 
     // ---- walk 2: the gradient of bands [k0, k1) ----
     float* pg = a.g + img;
-    f32x4 yv = sl_load<VEC>(py + sl_band(k0, C) * a.plane, nv), c = sl_load<VEC>(pc + sl_band(k0, C) * a.plane, nv);
-    f32x4 yn = sl_load<VEC>(py + sl_band(k0 + 1, C) * a.plane, nv), cn = sl_load<VEC>(pc + sl_band(k0 + 1, C) * a.plane, nv);
-    f32x4 x = sl_clamp01(yv);
+    f32x4 yv = load4_if(py + sl_band(k0, C) * a.plane, VEC, nv), c = load4_if(pc + sl_band(k0, C) * a.plane, VEC, nv);
+    f32x4 yn = load4_if(py + sl_band(k0 + 1, C) * a.plane, VEC, nv), cn = load4_if(pc + sl_band(k0 + 1, C) * a.plane, VEC, nv);
+    f32x4 x = clamp01(yv);
     float sprev[4] = {0.f, 0.f, 0.f, 0.f};                                   // sign(e_{k-1})
     if (a.do_sd && k0 > 0) {
-        const f32x4 xp = sl_clamp01(sl_load<VEC>(py + (long)(k0 - 1) * a.plane, nv)), cp = sl_load<VEC>(pc + (long)(k0 - 1) * a.plane, nv);
+        const f32x4 xp = clamp01(load4_if(py + (long)(k0 - 1) * a.plane, VEC, nv)), cp = load4_if(pc + (long)(k0 - 1) * a.plane, VEC, nv);
 #pragma unroll
         for (int j = 0; j < 4; ++j) sprev[j] = sl_sign(sl_e(x[j], xp[j], c[j], cp[j]));
     }
     for (int k = k0; k < k1; ++k) {
-        const f32x4 y2 = sl_load<VEC>(py + sl_band(k + 2, C) * a.plane, nv), c2 = sl_load<VEC>(pc + sl_band(k + 2, C) * a.plane, nv);
-        const f32x4 xn = sl_clamp01(yn);
+        const f32x4 y2 = load4_if(py + sl_band(k + 2, C) * a.plane, VEC, nv), c2 = load4_if(pc + sl_band(k + 2, C) * a.plane, VEC, nv);
+        const f32x4 xn = clamp01(yn);
         f32x4 gv;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -203,7 +172,7 @@ template <bool VEC> __global__ __launch_bounds__(SL_NT) void spectral_loss_kerne
             gv[j] = (yv[j] >= 0.f && yv[j] <= 1.f) ? (gl1 + gsd) + gsam : 0.f;
             sprev[j] = se;
         }
-        sl_store<VEC>(pg + (long)k * a.plane, gv, nv);
+        store4_if(pg + (long)k * a.plane, gv, VEC, nv);
         x = xn;
         yv = yn;
         c = cn;
@@ -227,9 +196,9 @@ __global__ __launch_bounds__(SL_NT) void spectral_loss_finish_kernel(SpectralLos
         s1 += a.ws[3 * i + 1];
         s2 += a.ws[3 * i + 2];
     }
-    s0 = sl_wave_sum(s0);
-    s1 = sl_wave_sum(s1);
-    s2 = sl_wave_sum(s2);
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
     if (lane == 0) {
         red[wave][0] = s0;
         red[wave][1] = s1;
@@ -237,9 +206,9 @@ __global__ __launch_bounds__(SL_NT) void spectral_loss_finish_kernel(SpectralLos
     }
     __syncthreads();
     if (t != 0) return;
-    const double l1 = (((red[0][0] + red[1][0]) + red[2][0]) + red[3][0]) * a.inv_n;
-    const double sam = a.w_sam != 0.0 ? (((red[0][1] + red[1][1]) + red[2][1]) + red[3][1]) * a.inv_p : 0.0;
-    const double sdf = a.w_sd != 0.0 ? (((red[0][2] + red[1][2]) + red[2][2]) + red[3][2]) * a.inv_sd : 0.0;
+    const double l1 = sum4_ordered(&red[0][0], 3) * a.inv_n;
+    const double sam = a.w_sam != 0.0 ? sum4_ordered(&red[0][1], 3) * a.inv_p : 0.0;
+    const double sdf = a.w_sd != 0.0 ? sum4_ordered(&red[0][2], 3) * a.inv_sd : 0.0;
     a.out[0] = (float)((l1 + a.w_sam * sam) + a.w_sd * sdf);
     a.out[1] = (float)l1;
     a.out[2] = (float)sam;
@@ -280,8 +249,7 @@ extern "C" int mphsir_spectral_loss(const mphsir_spectral_loss_args* a, void* st
                       (int)(nblk / a->B), a->w_sam != 0.f, do_sd, (double)a->w_sam / P, (float)(1.0 / n),
                       do_sd ? (float)((double)a->w_sdiff / n_sd) : 0.f};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool vec = a->W % 4 == 0 && aligned16(a->y) && aligned16(a->clean) && aligned16(a->grad);
-    if (vec)
+    if (rows_aligned16(a->W, a->y, a->clean, a->grad))
         MPHSIR_LAUNCH(MPHSIR_K_SPECTRAL_LOSS, spectral_loss_kernel<true>, dim3((unsigned)nblk), dim3(SL_NT), 0, s, d);
     else
         MPHSIR_LAUNCH(MPHSIR_K_SPECTRAL_LOSS, spectral_loss_kernel<false>, dim3((unsigned)nblk), dim3(SL_NT), 0, s, d);

@@ -511,6 +511,14 @@ def l1_clamp_loss_grad(y, clean):
     return _l1_clamp_loss_launch(y, clean, True)
 
 
+def _workspace_bytes(op, refusal, *sizes):
+    """what mphsir_<op>_workspace_bytes answers for these sizes; a negative answer raises `refusal`, formatted with them"""
+    nbytes = getattr(_lib.load(), "mphsir_%s_workspace_bytes" % op)(*sizes)
+    if nbytes < 0:
+        raise RuntimeError("mp-hsir_amd: " + refusal % sizes)
+    return nbytes
+
+
 _SPECTRAL_WS = {}      # (device, stream, bytes) -> the float64 block partials of mphsir_spectral_loss, reused from call to call
 
 
@@ -518,9 +526,7 @@ def spectral_loss_workspace(y):
     """the workspace mphsir_spectral_loss needs for a (B,C,H,W) cube like y, one per (device, stream, size): launch 2 has consumed it
     when the call returns to the stream, so the next call on that stream may overwrite it"""
     B, C, H, W = y.shape
-    nbytes = _lib.load().mphsir_spectral_loss_workspace_bytes(B, C, H, W)
-    if nbytes < 0:
-        raise RuntimeError("mp-hsir_amd: spectral_loss refuses (B %d, C %d, H %d, W %d)" % (B, C, H, W))
+    nbytes = _workspace_bytes("spectral_loss", "spectral_loss refuses (B %d, C %d, H %d, W %d)", B, C, H, W)
     key = (y.device, torch.cuda.current_stream(y.device).cuda_stream if y.is_cuda else 0, nbytes)
     ws = _SPECTRAL_WS.get(key)
     if ws is None:
@@ -826,9 +832,7 @@ def quality_bands(restored, clean, out=None):
     assert restored.is_contiguous() and clean.is_contiguous(), "quality_bands: contiguous inputs"
     assert restored.device == clean.device, "quality_bands: inputs on %s and %s" % (restored.device, clean.device)
     B, C, H, W = restored.shape if restored.dim() == 4 else (1,) + tuple(restored.shape)
-    nbytes = lib.mphsir_quality_workspace_bytes(B, C, H, W)
-    if nbytes < 0:
-        raise RuntimeError("mp-hsir_amd: quality_bands refuses (B %d, C %d, H %d, W %d): H, W >= 7, B, C <= 65535, H * W < 2^31" % (B, C, H, W))
+    nbytes = _quality_workspace_bytes(B, C, H, W)
     dev = restored.device
     if out is None:
         out = quality_buffers(B, C, H, W, dev)
@@ -844,12 +848,14 @@ def quality_bands(restored, clean, out=None):
     return psnr, ssim, sam, npix
 
 
+def _quality_workspace_bytes(B, C, H, W):
+    return _workspace_bytes("quality", "quality_bands refuses (B %d, C %d, H %d, W %d): H, W >= 7, B, C <= 65535, H * W < 2^31", B, C, H, W)
+
+
 def quality_buffers(B, C, H, W, device):
     """-> (psnr (B,C) f64, ssim (B,C) f64, sam_deg (B,) f64, sam_pixels (B,) i64, workspace f64): the outputs and the scratch of
     quality_bands for these sizes, uninitialised"""
-    nbytes = _lib.load().mphsir_quality_workspace_bytes(B, C, H, W)
-    if nbytes < 0:
-        raise RuntimeError("mp-hsir_amd: quality_bands refuses (B %d, C %d, H %d, W %d): H, W >= 7, B, C <= 65535, H * W < 2^31" % (B, C, H, W))
+    nbytes = _quality_workspace_bytes(B, C, H, W)
     return (torch.empty((B, C), dtype=torch.float64, device=device), torch.empty((B, C), dtype=torch.float64, device=device),
             torch.empty((B,), dtype=torch.float64, device=device), torch.empty((B,), dtype=torch.int64, device=device),
             torch.empty((nbytes // 8,), dtype=torch.float64, device=device))
@@ -905,6 +911,15 @@ class DegradePlan:
             raise TypeError("DegradePlan: unknown tables %s" % sorted(tables))
 
 
+def _out_pair(clean, out, want_clean):
+    """out = (degraded, clean_aug | None) for the batch `clean`: allocated when not given, every cube of it checked against the batch"""
+    if out is None:
+        out = (torch.empty_like(clean), torch.empty_like(clean) if want_clean else None)
+    for t in out:
+        assert t is None or (t.shape == clean.shape and t.dtype == torch.float32 and t.is_contiguous() and t.device == clean.device)
+    return out
+
+
 def _degrade(fn, clean, plan, seed, ordinal, draws, out, want_clean=True):
     """what degrade_batch and degrade_planes share: the checks of the cube, the plan's tables, the draws and the outputs, and the call.
     out = (degraded, clean_aug | None)"""
@@ -924,10 +939,7 @@ def _degrade(fn, clean, plan, seed, ordinal, draws, out, want_clean=True):
             "%s: explicit draws are contiguous fp32 cubes of the batch's shape" % fn
     if od is not None:
         assert od.dtype == torch.int64 and od.numel() == 1 and od.device == clean.device, "%s: a device ordinal is one int64" % fn
-    if out is None:
-        out = (torch.empty_like(clean), torch.empty_like(clean) if want_clean else None)
-    for t in out:
-        assert t is None or (t.shape == clean.shape and t.dtype == torch.float32 and t.is_contiguous() and t.device == clean.device)
+    out = _out_pair(clean, out, want_clean)
     ptrs = [clean.data_ptr()] + [t.data_ptr() for t in out if t is not None]
     assert out[0] is not None and len(set(ptrs)) == len(ptrs), "%s: distinct cubes" % fn
     host = [(ctypes.c_int32 * max(len(v), 1))(*v) for v in (plan.menu, plan.ksize, plan.sr_factor)]
@@ -975,9 +987,7 @@ def patch_sample(arena, levels, levels_host, records, index, C, P, out=None, wor
     assert records.dim() == 2 and records.shape[1] == 3 and records.dtype == torch.int32 and records.is_contiguous(), "patch_sample: records is (n,3) int32"
     assert index is None or (index.dim() == 1 and index.dtype == torch.int64 and index.is_contiguous()), "patch_sample: index is (B,) int64"
     B = records.shape[0] if index is None else index.shape[0]
-    nbytes = lib.mphsir_patch_sample_workspace_bytes(B, C)
-    if nbytes < 0:
-        raise RuntimeError("mp-hsir_amd: patch_sample refuses (B %d, C %d): both in 1..65535" % (B, C))
+    nbytes = _workspace_bytes("patch_sample", "patch_sample refuses (B %d, C %d): both in 1..65535", B, C)
     dev = arena.device
     if workspace is None:
         workspace = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
@@ -1010,18 +1020,13 @@ def cassi(clean, mask, origin=None, step=2, aug=None, task=None, task_id=0, want
         "cassi: origin is (B,2) int32"
     for name, t in (("aug", aug), ("task", task)):
         assert t is None or (t.dtype == torch.int32 and tuple(t.shape) == (B,) and t.is_contiguous() and t.device == dev), "cassi: %s is (B,) int32" % name
-    nbytes = lib.mphsir_cassi_workspace_bytes(B, C, H, W, int(step))
-    if nbytes < 0:
-        raise RuntimeError("mp-hsir_amd: cassi refuses (B %d, C %d, H %d, W %d, step %d): B, C in 1..65535, step in 1..8, planes below 2^31 elements"
-                           % (B, C, H, W, step))
+    nbytes = _workspace_bytes("cassi", "cassi refuses (B %d, C %d, H %d, W %d, step %d): B, C in 1..65535, step in 1..8, planes below 2^31 elements",
+                              B, C, H, W, int(step))
     if workspace is None:
         workspace = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
     assert workspace.dtype == torch.float32 and workspace.is_contiguous() and workspace.device == dev
-    if out is None:
-        out = (torch.empty_like(clean), torch.empty_like(clean) if want_clean_aug else None)
-    assert len(out) == 2 and out[0] is not None, "cassi: out = (degraded, clean_aug or None)"
-    for t in out:
-        assert t is None or (t.shape == clean.shape and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev)
+    assert out is None or (len(out) == 2 and out[0] is not None), "cassi: out = (degraded, clean_aug or None)"
+    out = _out_pair(clean, out, want_clean_aug)
     a = _lib.CassiArgs(clean=_p(clean), mask=_p(mask), origin=_p(origin), task=_p(task), aug=_p(aug), degraded=_p(out[0]), clean_aug=_p(out[1]),
                        workspace=_p(workspace), workspace_bytes=workspace.numel() * 4, B=B, C=C, H=H, W=W, MH=mask.shape[0], MW=mask.shape[1],
                        step=int(step), task_id=int(task_id))
@@ -1505,9 +1510,7 @@ def new_optim_stats(device):
 
 def grad_norm_workspace(g):
     """the float64 block partials mphsir_grad_norm needs for the arena g (caller-owned: a captured launch keeps its address)"""
-    nbytes = _lib.load().mphsir_grad_norm_workspace_bytes(g.numel())
-    if nbytes < 0:
-        raise RuntimeError("mp-hsir_amd: grad_norm refuses an arena of %d elements (a positive multiple of 4)" % g.numel())
+    nbytes = _workspace_bytes("grad_norm", "grad_norm refuses an arena of %d elements (a positive multiple of 4)", g.numel())
     return torch.empty((nbytes // 8,), dtype=torch.float64, device=g.device)
 
 

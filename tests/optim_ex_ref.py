@@ -12,7 +12,7 @@ import math
 import numpy as np
 import torch
 
-from util import rel_l2
+from util import bits, rel_l2, ulp32  # noqa: F401  (the tests reach them through this module)
 
 # one vector; less than a full block plus a tail vector; just past a block multiple; many blocks, still small enough for the emulator
 SIZES = [4, 1028, 3 * 1024 + 4, 2 ** 16 + 8]
@@ -35,10 +35,6 @@ def normals(n, seed, dev="cpu", scale=1.0):
 
 def f64(t):
     return t.detach().cpu().numpy().astype(np.float64)
-
-
-def bits(t):
-    return t.detach().cpu().numpy().tobytes()
 
 
 # ---- the restatement ------------------------------------------------------------------------------------------------------------------------
@@ -86,10 +82,6 @@ class RefState:
             errs["ema"] = rel_l2(ema.cpu(), self.ema)
         print("%s rel-L2 %s (bar %.1g)" % (what, {k: "%.3g" % e for k, e in errs.items()}, BAR))
         assert all(e < BAR for e in errs.values()), (what, errs)
-
-
-def ulp32(x):
-    return float(np.spacing(np.float32(abs(x))))
 
 
 # ---- kernel checks --------------------------------------------------------------------------------------------------------------------------

@@ -11,6 +11,8 @@ import sys
 import numpy as np
 import torch
 
+from util import same_floats  # noqa: F401  (the tests reach it through this module)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
@@ -25,12 +27,6 @@ def numpy_patches(arena, levels, triples, C, P):
             assert p.shape == (C, P, P) and p.dtype == np.float32
             out.append((p - p.min()) / (p.max() - p.min()))
     return np.stack(out)
-
-
-def same_floats(got, want):
-    got, want = np.asarray(got), np.asarray(want)
-    nan = np.isnan(want)
-    return got.shape == want.shape and np.array_equal(np.isnan(got), nan) and np.array_equal(got[~nan], want[~nan])
 
 
 class Tables:

@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 import guard
-from optim_ex_ref import ConvNet, as_f32, bits, f64
+from optim_ex_ref import ConvNet, as_f32, f64
+from util import bits, ulp32  # noqa: F401  (the tests reach them through this module)
 
 MIN_SIN = 1e-6                      # MPHSIR_SAM_MIN_SIN of include/mphsir.h (tests/test_spectral_loss_meta.py compares the two)
 WEIGHTS = [(0.1, 0.0), (0.0, 0.3), (0.1, 0.3)]
@@ -26,10 +27,6 @@ WEIGHTS = [(0.1, 0.0), (0.0, 0.3), (0.1, 0.3)]
 # (100 = 4 x 25, 172 = 4 x 43, and 3 / 8 / 31 split unevenly over the four waves); the training patch: several workgroups per image
 SHAPES = [(1, 1, 4, 4), (1, 3, 4, 5), (3, 8, 5, 7), (2, 31, 16, 16), (2, 100, 8, 8), (1, 172, 4, 8), (2, 31, 64, 64)]
 SHAPE_GPU = (4, 31, 64, 64)         # GPU only, 4 bytes past a 16-byte boundary: the scalar path at a size the 16-byte path is built for
-
-
-def ulp32(x):
-    return np.spacing(np.abs(np.asarray(x, dtype=np.float64)).astype(np.float32)).astype(np.float64)
 
 
 def make_inputs(shape, seed=0):

@@ -1,21 +1,11 @@
 """The two CASSI kernels (mp-hsir_amd/csrc/cassi.hip) in the built code object (CPU test): stable names, no register spills, no scratch,
 and the register / LDS figures DESIGN.md section 5 states: at most 32 (measure) and 48 (emit) VGPRs and 48 bytes of LDS per workgroup of
 256 threads, so neither limits residency -- a CU holds its maximum of 8 such workgroups (32 waves, 8 per SIMD, which needs <= 64 VGPRs)."""
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import meta
 
 
 def test_cassi_kernels_do_not_spill_and_fit_full_occupancy():
-    build = os.path.join(ROOT, "mp-hsir_amd", "build")
-    if not os.path.exists(os.path.join(build, "cassi.o")):
-        sys.path.insert(0, os.path.join(ROOT, "mp-hsir_amd"))
-        import build as B
-        B.build(verbose=False)
-    import kernel_meta
-    ks = {k["demangled"].split("(")[0]: k for k in kernel_meta.object_kernels(os.path.join(build, "cassi.o"))}
+    ks = {k["demangled"].split("(")[0]: k for k in meta.object_kernels("cassi")}
     assert sorted(ks) == ["mphsir::cassi_emit_kernel", "mphsir::cassi_measure_kernel"], sorted(ks)
     for name, k in ks.items():
         assert k.get("vgpr_spill_count", 0) == 0 and k.get("sgpr_spill_count", 0) == 0 and k.get("private_segment_fixed_size", 0) == 0, k

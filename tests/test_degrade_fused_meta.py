@@ -1,20 +1,10 @@
 """The fused degradation kernel (mp-hsir_amd/csrc/degrade.hip) in the built code object: present, no register spills, no scratch, and the
 register count the occupancy it is laid out for needs (CPU test, as tests/test_ensemble_meta.py)."""
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import meta
 
 
 def test_degrade_kernel_does_not_spill_and_keeps_five_workgroups_per_cu():
-    build = os.path.join(ROOT, "mp-hsir_amd", "build")
-    if not os.path.exists(os.path.join(build, "degrade.o")):
-        sys.path.insert(0, os.path.join(ROOT, "mp-hsir_amd"))
-        import build as B
-        B.build(verbose=False)
-    import kernel_meta
-    ks = [k for k in kernel_meta.all_kernels(build) if "degrade_batch_kernel" in k["name"]]
+    ks = [k for k in meta.object_kernels("degrade") if "degrade_batch_kernel" in k["name"]]
     assert len(ks) == 2, "two instances, generated and explicit draws: %s" % [k["name"] for k in ks]
     for k in ks:
         assert k.get("vgpr_spill_count", 0) == 0 and k.get("sgpr_spill_count", 0) == 0 and k.get("private_segment_fixed_size", 0) == 0, k

@@ -1,11 +1,7 @@
 """The tiled degradation kernel (mp-hsir_amd/csrc/degrade.hip, degrade_planes_kernel) in the built code object: its four instances are
 present, spill nothing, use no scratch and no static LDS, and keep the register count of the occupancy the file's header claims (CPU
 test, as tests/test_degrade_fused_meta.py)."""
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import meta
 
 
 def planes_lds_bytes(hmax, factors, blur):
@@ -19,13 +15,7 @@ def planes_lds_bytes(hmax, factors, blur):
 
 
 def test_planes_kernel_instances_do_not_spill_and_keep_five_workgroups_per_cu():
-    build = os.path.join(ROOT, "mp-hsir_amd", "build")
-    if not os.path.exists(os.path.join(build, "degrade.o")):
-        sys.path.insert(0, os.path.join(ROOT, "mp-hsir_amd"))
-        import build as B
-        B.build(verbose=False)
-    import kernel_meta
-    ks = [k for k in kernel_meta.all_kernels(build) if "degrade_planes_kernel" in k["name"]]
+    ks = [k for k in meta.object_kernels("degrade") if "degrade_planes_kernel" in k["name"]]
     assert len(ks) == 4, "generated / explicit draws x dwordx4 / scalar access: %s" % [k["name"] for k in ks]
     for k in ks:
         assert k.get("vgpr_spill_count", 0) == 0 and k.get("sgpr_spill_count", 0) == 0 and k.get("private_segment_fixed_size", 0) == 0, k

@@ -1,20 +1,10 @@
 """The two self-ensemble kernels (mp-hsir_amd/csrc/scene_d4.hip) in the built code objects: no register spills, no scratch, and the
 register budget the two scene kernels are held to (CPU test, as tests/test_scene_meta.py)."""
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import meta
 
 
 def test_d4_kernels_do_not_spill():
-    build = os.path.join(ROOT, "mp-hsir_amd", "build")
-    if not os.path.exists(os.path.join(build, "scene_d4.o")):
-        sys.path.insert(0, os.path.join(ROOT, "mp-hsir_amd"))
-        import build as B
-        B.build(verbose=False)
-    import kernel_meta
-    ks = [k for k in kernel_meta.all_kernels(build) if "d4_gather_kernel" in k["name"] or "d4_fold_kernel" in k["name"]]
+    ks = [k for k in meta.object_kernels("scene_d4") if "d4_gather_kernel" in k["name"] or "d4_fold_kernel" in k["name"]]
     assert sorted("gather" in k["name"] for k in ks) == [False, True], [k["name"] for k in ks]
     for k in ks:
         assert k.get("vgpr_spill_count", 0) == 0 and k.get("sgpr_spill_count", 0) == 0 and k.get("private_segment_fixed_size", 0) == 0, k

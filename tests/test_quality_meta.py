@@ -5,24 +5,14 @@ Planned occupancy of quality_partials_kernel: TWO workgroups of 256 threads per 
 gfx950 CU then allow 80 KiB per workgroup (the kernel holds a double-buffered fp32 stage of both cubes and five planes of fp64 row
 sums: about 70 KiB), and 2 waves per SIMD allow 256 VGPRs per lane.  The second workgroup is what runs while the first waits at one of
 its two barriers per band.  quality_finish_kernel is one wave per workgroup without LDS."""
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+import meta
 
 LDS_PER_CU = 160 * 1024
 WORKGROUPS_PER_CU = 2
 
 
 def test_quality_kernels_fit_the_planned_occupancy_and_do_not_spill():
-    build = os.path.join(ROOT, "mp-hsir_amd", "build")
-    if not os.path.exists(os.path.join(build, "quality.o")):
-        sys.path.insert(0, os.path.join(ROOT, "mp-hsir_amd"))
-        import build as B
-        B.build(verbose=False)
-    import kernel_meta
-    ks = {k["demangled"].split("(")[0]: k for k in kernel_meta.object_kernels(os.path.join(build, "quality.o"))}
+    ks = {k["demangled"].split("(")[0]: k for k in meta.object_kernels("quality")}
     assert sorted(ks) == ["mphsir::quality_finish_kernel", "mphsir::quality_partials_kernel"], sorted(ks)
     for k in ks.values():
         assert k.get("vgpr_spill_count", 0) == 0 and k.get("sgpr_spill_count", 0) == 0 and k.get("private_segment_fixed_size", 0) == 0, k

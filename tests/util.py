@@ -1,7 +1,27 @@
 """Helpers shared by the tests: deterministic parameter dicts built from the committed manifest."""
+import numpy as np
 import torch
 
 from golden.detfill import det_value
+
+
+def bits(t):
+    """the bytes of a tensor of any dtype (numpy has no bfloat16: through a byte view) or of a numpy array"""
+    if torch.is_tensor(t):
+        return t.detach().contiguous().reshape(-1).view(torch.uint8).cpu().numpy().tobytes()
+    return np.ascontiguousarray(t).tobytes()
+
+
+def same_floats(got, want):
+    """equal shapes, NaN at the same places, equal values everywhere else"""
+    got, want = np.asarray(got), np.asarray(want)
+    nan = np.isnan(want)
+    return got.shape == want.shape and np.array_equal(np.isnan(got), nan) and np.array_equal(got[~nan], want[~nan])
+
+
+def ulp32(x):
+    """the spacing of fp32 at |x| (a number or an array), as float64"""
+    return np.spacing(np.abs(np.asarray(x, dtype=np.float64)).astype(np.float32)).astype(np.float64)
 
 
 def params_from_manifest(man, prefix="", dtype=torch.float64, rename_from=None):

@@ -4,10 +4,7 @@ import numpy as np
 import torch
 
 import spectral_loss_ref as S
-
-def bits(t):
-    """the bytes of a tensor of any dtype (numpy has no bfloat16: through a byte view)"""
-    return t.detach().contiguous().reshape(-1).view(torch.uint8).cpu().numpy().tobytes()
+from util import bits  # noqa: F401  (the tests reach it through this module)
 
 
 def make_vset(dev, kind, net=None, seed=11):
