@@ -116,6 +116,58 @@ def active():
     return _ACTIVE[0]
 
 
+# ---- recorder (tests/test_emu_schedules.py) -------------------------------------------------------------------------------------
+# Inactive by default.  While `recording()` is active, every tensor a check compares -- kernel_checks.close's `got`, both sides of a
+# torch.equal -- and, when a guarded check ends, every non-input buffer the guard handed out (what ops.py allocated for a kernel to
+# write: results, workspaces, partials) is appended to a list as a CPU clone.  Nothing is asserted here and no comparison changes: two
+# runs of the same check under two schedules of the emulator are compared record by record, bit by bit, by the caller.
+_RECORD = [None]
+
+
+def record(tensor, what=""):
+    if _RECORD[0] is not None and isinstance(tensor, _torch.Tensor):
+        _RECORD[0].append((what, tensor.detach().cpu().contiguous().clone()))
+
+
+class recording:
+    def __enter__(self):
+        assert _RECORD[0] is None, "recording() does not nest"
+        self.saved_equal = _torch.equal
+        real = self.saved_equal
+
+        def equal(a, b):
+            record(a, "equal lhs")
+            record(b, "equal rhs")
+            return real(a, b)
+        _torch.equal = equal
+        _RECORD[0] = []
+        return _RECORD[0]
+
+    def __exit__(self, *exc):
+        _torch.equal = self.saved_equal
+        _RECORD[0] = None
+        return False
+
+
+def first_difference(a, b):
+    """None when two recorded tensors hold the same bits (a NaN equals itself), else a description of the first differing element"""
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return "shape / dtype %s %s against %s %s" % (tuple(a.shape), a.dtype, tuple(b.shape), b.dtype)
+    if a.numel() == 0:
+        return None
+    ia, ib = a.reshape(-1).view(_torch.uint8), b.reshape(-1).view(_torch.uint8)
+    if _torch.equal(ia, ib):
+        return None
+    flat = int((ia != ib).nonzero()[0]) // a.element_size()
+    idx, rest = [], flat
+    for n in reversed(a.shape):
+        idx.append(rest % n)
+        rest //= n
+    n_diff = int((ia != ib).reshape(-1, a.element_size()).any(1).sum())
+    return "%d of %d elements differ, first at index %s (flat %d): %r against %r" % (
+        n_diff, a.numel(), tuple(reversed(idx)), flat, a.reshape(-1)[flat].item(), b.reshape(-1)[flat].item())
+
+
 class Report(AssertionError):
     pass
 
@@ -423,6 +475,10 @@ def guarded(fn):
             try:
                 res = fn(dev, *a, **kw)
                 report = g.verify()
+                if _RECORD[0] is not None:
+                    for b in g.bufs:
+                        if b.role != "input":
+                            record(b.view, "%s:%d %s -> %s" % (b.site[3], b.site[2], b.site[0], b.site[1]))
             finally:
                 st = STATS.setdefault(fn.__module__, [0, 0, {}])
                 st[0] += 1

@@ -3,6 +3,9 @@
 
 The emulated library exports the same C ABI as libmphsir.so and is loaded only by tests (see
 tests/emu.py) to check kernel logic on machines without a GPU.  The product never loads it.
+
+build_selftest() compiles tests/hipemu/selftest.hip (kernels with planted synchronisation faults for the emulator's schedules,
+tests/test_emu_schedules.py) into libhipemu_selftest.so beside it: a library of its own, never part of libmphsir_emu.so.
 """
 import os
 import subprocess
@@ -17,6 +20,10 @@ CSRC = os.path.join(ROOT, "mp-hsir_amd", "csrc")
 SANITIZE = os.environ.get("HIPEMU_SANITIZE", "0") == "1"
 BUILD = os.path.join(HERE, "_build_asan" if SANITIZE else "_build")
 OUT = os.path.join(BUILD, "libmphsir_emu.so")
+# kernels with planted synchronisation faults for the emulator's schedules (tests/test_emu_schedules.py): a library of its own,
+# outside csrc/, never linked into libmphsir_emu.so
+SELFTEST_SRC = os.path.join(HERE, "selftest.hip")
+SELFTEST_OUT = os.path.join(BUILD, "libhipemu_selftest.so")
 CXX = os.environ.get("HIPEMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")
 FLAGS = ["-x", "c++", "-std=c++17", "-O2", "-g", "-fPIC", "-ffp-contract=off", "-mavx2", "-mfma", "-mf16c",
          "-I", os.path.join(HERE, "include"), "-Wno-unused-function", "-Wno-unknown-attributes",
@@ -40,6 +47,22 @@ def _compile(src, dep_mtime):
     return obj
 
 
+def build_selftest():
+    """tests/hipemu/selftest.hip -> libhipemu_selftest.so (its own copy of the emulator's scheduler); rebuilt when the source or the
+    emulator's header is newer"""
+    os.makedirs(BUILD, exist_ok=True)
+    newest = max(os.path.getmtime(SELFTEST_SRC), os.path.getmtime(os.path.join(HERE, "include", "hip", "hip_runtime.h")))
+    if os.path.exists(SELFTEST_OUT) and os.path.getmtime(SELFTEST_OUT) > newest:
+        return SELFTEST_OUT
+    # always without the sanitizers: the library is there to test the scheduler and the LDS poison, and the poison of static LDS is
+    # what the AddressSanitizer build of the header leaves out
+    flags = [f for f in FLAGS if "sanitize" not in f and f != "-shared-libasan"]
+    r = subprocess.run([CXX] + flags + ["-DHIPEMU_IMPLEMENTATION", "-shared", SELFTEST_SRC, "-o", SELFTEST_OUT], capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("hipemu selftest build failed:\n%s" % r.stderr[-8000:])
+    return SELFTEST_OUT
+
+
 def build(jobs=6):
     os.makedirs(BUILD, exist_ok=True)
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
@@ -57,3 +80,4 @@ def build(jobs=6):
 
 if __name__ == "__main__":
     print(build())
+    print(build_selftest())

@@ -11,6 +11,16 @@
 // __syncthreads() and the wave-collective operations (shuffles, MFMA) are rendezvous points.
 // A wave is 64 consecutive work-items.  Wave collectives must be reached by all 64 lanes (as on the
 // hardware: MFMA needs EXEC all ones).  Global memory is host memory.
+//
+// Schedules: the order in which the scheduler resumes the fibers of a workgroup (and walks the blocks of a grid) is set through
+// hipemu_set_schedule(mode, seed).  A kernel that orders its LDS traffic with barriers gives the same bits under every one of them;
+// a kernel that misses a barrier gives different bits under some (tests/test_emu_schedules.py, tests/hipemu/selftest.hip).
+//   0  ascending thread order (the default)          3  seeded random wave order and lane order, re-drawn at every pass
+//   1  descending thread order                       4  laggard: wave seed % nwaves runs only in a pass in which no other fiber moved
+//   2  descending wave order, lanes ascending        5  sprinter: wave seed % nwaves runs until it is stuck before any other wave
+//   | HIPEMU_SCHED_DESC_BLOCKS: the blocks of a grid in descending order.
+// Static and dynamic LDS are filled with 0xCD before every block.  A scheduler pass that resumed every live fiber and saw none of
+// them leave a rendezvous or finish is a deadlock (a barrier not every thread reaches): reported and aborted.
 // ================================================================================================
 #pragma once
 #include <cmath>
@@ -27,7 +37,23 @@
 #define __host__
 #define __forceinline__ inline __attribute__((always_inline))
 #define __launch_bounds__(...)
+// static LDS objects are collected in one section of the library so that run_block can poison them (the linker provides the bounds)
+// (not in the AddressSanitizer build, HIPEMU_SANITIZE=1: a global in a named section gets no red zones, and that build is there for
+// the out-of-tile index; the section is then empty and nothing is poisoned)
+#if defined(__has_feature)
+#if __has_feature(address_sanitizer)
+#define HIPEMU_PLAIN_STATIC_LDS 1
+#endif
+#endif
+#ifdef HIPEMU_PLAIN_STATIC_LDS
 #define __shared__ static
+#else
+#define __shared__ static __attribute__((section("hipemu_lds")))
+#endif
+extern "C" char __start_hipemu_lds[] __attribute__((weak, visibility("hidden")));
+extern "C" char __stop_hipemu_lds[] __attribute__((weak, visibility("hidden")));
+#define HIPEMU_SCHED_MODE_MASK 0xff
+#define HIPEMU_SCHED_DESC_BLOCKS 0x100
 #define HIP_DYNAMIC_SHARED(type, var) type* var = reinterpret_cast<type*>(hipemu::dyn_lds());
 
 struct dim3 {
@@ -67,6 +93,7 @@ struct Fiber {
     dim3 tid;
     int flat;
     bool done;
+    int wait;           // 0 running, 1 at the block barrier, 2 at a wave rendezvous
 };
 
 struct WaveState {
@@ -86,6 +113,10 @@ struct State {
     char* stacks = nullptr;
     std::vector<unsigned char> lds;
     std::function<void()> body;
+    int sched = 0;                  // mode | flags (hipemu_set_schedule)
+    uint64_t sched_seed = 0, rng = 0;
+    uint64_t progress = 0;          // a fiber left a rendezvous or finished
+    int max_waves = 0;              // the widest workgroup launched since the last hipemu_set_schedule
 };
 
 inline State& S() { static State s; return s; }
@@ -116,12 +147,39 @@ hipemu_switch:
 )");
 #endif
 
+extern "C" void hipemu_set_schedule(int mode, uint64_t seed);
+extern "C" int hipemu_get_schedule(uint64_t* seed);
+extern "C" int hipemu_max_waves();      // waves of the widest workgroup launched since the last hipemu_set_schedule: what modes 4 and 5 can name
+#ifdef HIPEMU_IMPLEMENTATION
+extern "C" void hipemu_set_schedule(int mode, uint64_t seed) {
+    State& s = S();
+    if ((mode & HIPEMU_SCHED_MODE_MASK) > 5 || (mode & ~(HIPEMU_SCHED_MODE_MASK | HIPEMU_SCHED_DESC_BLOCKS)) || mode < 0) {
+        fprintf(stderr, "hipemu: unknown schedule 0x%x\n", mode); abort();
+    }
+    s.sched = mode; s.sched_seed = seed; s.rng = seed; s.max_waves = 0;
+}
+extern "C" int hipemu_max_waves() { return S().max_waves; }
+extern "C" int hipemu_get_schedule(uint64_t* seed) { if (seed) *seed = S().sched_seed; return S().sched; }
+#endif
+
+// splitmix64: the generator of the random schedule (fixed here so that a seed names one schedule on every machine)
+inline uint64_t sched_rand() {
+    uint64_t z = (S().rng += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+inline void sched_shuffle(int* v, int n) {
+    for (int i = n - 1; i > 0; --i) { int j = (int)(sched_rand() % (uint64_t)(i + 1)); int t = v[i]; v[i] = v[j]; v[j] = t; }
+}
+
 inline void yield() { State& s = S(); hipemu_switch(&s.cur->sp, s.sched_sp); }
 
 inline void fiber_entry() {
     State& s = S();
     s.body();
     s.cur->done = true;
+    s.progress++;
     hipemu_switch(&s.cur->sp, s.sched_sp);
     abort();
 }
@@ -132,7 +190,8 @@ inline void block_sync() {
     State& s = S();
     int gen = s.bar_gen;
     if (++s.bar_count == s.nthreads) { s.bar_count = 0; s.bar_gen++; }
-    else while (s.bar_gen == gen) yield();
+    else { s.cur->wait = 1; while (s.bar_gen == gen) yield(); s.cur->wait = 0; }
+    s.progress++;
 }
 
 inline WaveState& my_wave() { State& s = S(); return s.waves[s.cur->flat / kWave]; }
@@ -145,7 +204,8 @@ inline void wave_sync() {
     int n = s.nthreads - first < kWave ? s.nthreads - first : kWave;
     int gen = w.gen;
     if (++w.count == n) { w.count = 0; w.gen++; }
-    else while (w.gen == gen) yield();
+    else { s.cur->wait = 2; while (w.gen == gen) yield(); s.cur->wait = 0; }
+    s.progress++;
 }
 
 template <class T> inline T wave_xchg(T v, int src_lane) {
@@ -159,6 +219,71 @@ template <class T> inline T wave_xchg(T v, int src_lane) {
     return r;
 }
 
+inline void resume(int t) {
+    State& s = S();
+    Fiber& f = s.fibers[t];
+    if (f.done) return;
+    s.cur = &f;
+    hipemu_switch(&s.sched_sp, f.sp);
+}
+inline void resume_wave(int w, const int* lanes) {
+    for (int l = 0; l < kWave; ++l) resume(w * kWave + (lanes ? lanes[l] : l));
+}
+
+[[noreturn]] inline void deadlock() {
+    State& s = S();
+    int at_block = 0, at_wave = 0, done = 0;
+    for (int t = 0; t < s.nthreads; ++t) {
+        at_block += s.fibers[t].wait == 1; at_wave += s.fibers[t].wait == 2; done += s.fibers[t].done;
+    }
+    fprintf(stderr, "hipemu: deadlock in block (%u,%u,%u) of grid (%u,%u,%u), %d threads: %d wait at the block barrier, %d at a wave "
+                    "rendezvous, %d have finished (schedule 0x%x seed %llu)\n", s.bid.x, s.bid.y, s.bid.z, s.gdim.x, s.gdim.y, s.gdim.z,
+            s.nthreads, at_block, at_wave, done, s.sched, (unsigned long long)s.sched_seed);
+    fflush(stderr);
+    abort();
+}
+
+// one scheduler pass: every live fiber is resumed at least once, in the order of the schedule
+inline void sched_pass() {
+    State& s = S();
+    const int n = s.nthreads, nw = n / kWave, mode = s.sched & HIPEMU_SCHED_MODE_MASK;
+    const int special = (int)(s.sched_seed % (uint64_t)nw);
+    switch (mode) {
+    default:
+        for (int t = 0; t < n; ++t) resume(t);
+        break;
+    case 1:
+        for (int t = n - 1; t >= 0; --t) resume(t);
+        break;
+    case 2:
+        for (int w = nw - 1; w >= 0; --w) resume_wave(w, nullptr);
+        break;
+    case 3: {
+        int waves[kMaxThreads / kWave], lanes[kWave];
+        for (int w = 0; w < nw; ++w) waves[w] = w;
+        sched_shuffle(waves, nw);
+        for (int i = 0; i < nw; ++i) {
+            for (int l = 0; l < kWave; ++l) lanes[l] = l;
+            sched_shuffle(lanes, kWave);
+            resume_wave(waves[i], lanes);
+        }
+        break;
+    }
+    case 4: {
+        const uint64_t p0 = s.progress;
+        for (int w = 0; w < nw; ++w) if (w != special) resume_wave(w, nullptr);
+        if (s.progress == p0) resume_wave(special, nullptr);
+        break;
+    }
+    case 5: {
+        uint64_t p0;
+        do { p0 = s.progress; resume_wave(special, nullptr); } while (s.progress != p0);
+        for (int w = 0; w < nw; ++w) if (w != special) resume_wave(w, nullptr);
+        break;
+    }
+    }
+}
+
 inline void run_block(dim3 bid, dim3 gdim, dim3 bdim, size_t shmem) {
     State& s = S();
     if (!s.stacks) {
@@ -169,13 +294,16 @@ inline void run_block(dim3 bid, dim3 gdim, dim3 bdim, size_t shmem) {
     s.bid = bid; s.gdim = gdim; s.bdim = bdim;
     s.nthreads = (int)(bdim.x * bdim.y * bdim.z);
     if (s.nthreads > kMaxThreads || s.nthreads % kWave) { fprintf(stderr, "hipemu: bad block size %d\n", s.nthreads); abort(); }
+    if (s.nthreads / kWave > s.max_waves) s.max_waves = s.nthreads / kWave;
     s.bar_count = 0; s.bar_gen = 0;
     for (auto& w : s.waves) { w.count = 0; w.gen = 0; }
     if (s.lds.size() < shmem + 64) s.lds.resize(shmem + 64);
     memset(s.lds.data(), 0xCD, s.lds.size());   // poison: reads of unwritten LDS show up as garbage
+    if (+__stop_hipemu_lds > +__start_hipemu_lds)  // static LDS of every kernel of the library: a block never sees what the last one left
+        memset(__start_hipemu_lds, 0xCD, (size_t)(__stop_hipemu_lds - __start_hipemu_lds));
     for (int t = 0; t < s.nthreads; ++t) {
         Fiber& f = s.fibers[t];
-        f.flat = t; f.done = false;
+        f.flat = t; f.done = false; f.wait = 0;
         f.tid = dim3(t % bdim.x, (t / bdim.x) % bdim.y, t / (bdim.x * bdim.y));
         void** top = (void**)(s.stacks + kStack * (t + 1));
         *--top = nullptr;                       // keeps rsp % 16 == 8 at fiber_entry's first instruction
@@ -183,15 +311,13 @@ inline void run_block(dim3 bid, dim3 gdim, dim3 bdim, size_t shmem) {
         for (int r = 0; r < 6; ++r) *--top = nullptr;
         f.sp = top;
     }
-    int remaining = s.nthreads;
-    while (remaining) {
-        for (int t = 0; t < s.nthreads; ++t) {
-            Fiber& f = s.fibers[t];
-            if (f.done) continue;
-            s.cur = &f;
-            hipemu_switch(&s.sched_sp, f.sp);
-            if (f.done) --remaining;
-        }
+    for (;;) {
+        int live = 0;
+        for (int t = 0; t < s.nthreads; ++t) live += !s.fibers[t].done;
+        if (!live) break;
+        const uint64_t p0 = s.progress;
+        sched_pass();
+        if (s.progress == p0) deadlock();       // every live fiber was resumed and none left its rendezvous
     }
     s.cur = nullptr;
 }
@@ -199,9 +325,12 @@ inline void run_block(dim3 bid, dim3 gdim, dim3 bdim, size_t shmem) {
 template <class K, class... A> inline void launch(K kern, dim3 grid, dim3 block, size_t shmem, A... args) {
     State& s = S();
     s.body = [=]() { kern(args...); };
-    for (unsigned z = 0; z < grid.z; ++z)
-        for (unsigned y = 0; y < grid.y; ++y)
-            for (unsigned x = 0; x < grid.x; ++x) run_block(dim3(x, y, z), grid, block, shmem);
+    const uint64_t nblocks = (uint64_t)grid.x * grid.y * grid.z;
+    const bool desc = (s.sched & HIPEMU_SCHED_DESC_BLOCKS) != 0;
+    for (uint64_t i = 0; i < nblocks; ++i) {    // ascending: x fastest, then y, then z; descending: the same walk backwards
+        const uint64_t b = desc ? nblocks - 1 - i : i;
+        run_block(dim3((unsigned)(b % grid.x), (unsigned)(b / grid.x % grid.y), (unsigned)(b / ((uint64_t)grid.x * grid.y))), grid, block, shmem);
+    }
 }
 
 }  // namespace hipemu

@@ -99,6 +99,7 @@ def close(got, ref, tol, geom=None, what="", whole=None):
     views an (M, C) token tensor as (B, H, W, C) so that image rows, image columns and samples are axes of their own.  Returns the
     whole-tensor value (`whole`: that value where the caller has computed it already)."""
     name = _calling_check()
+    guard.record(got, "close " + what)           # a no-op unless guard.recording() is active
     g, r = torch.as_tensor(got).detach().cpu(), torch.as_tensor(ref).detach().cpu()
     if whole is None:
         whole = _rel(g, r)
