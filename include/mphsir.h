@@ -1017,6 +1017,49 @@ typedef struct mphsir_spectral_loss_args mphsir_spectral_loss_args;
 int64_t mphsir_spectral_loss_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
 int mphsir_spectral_loss(const mphsir_spectral_loss_args* a, void* stream);
 
+/* ---- training loss: the SSIM term w_ssim * (1 - SSIM) and its gradient, one launch pair (off unless the caller asks:
+ * mp-hsir_amd/engine.py SpectralLoss(ssim=)) ------------------------------------------------------------------------------------------
+ * y (restored) and clean (c): fp32, contiguous (B, C, H, W), H, W >= 7.  x = clamp(y, 0, 1) with mphsir_l1_clamp_loss's NaN-propagating
+ * clamp.  SSIM is the one mphsir_quality reports (skimage's defaults at data range 1: uniform 7 x 7 window, sample covariance):
+ * N = 49, cov = 49 / 48, C1 = 1e-4, C2 = 9e-4; for every plane (b, k) and every one of the Nw = (H - 6)(W - 6) windows w that lie inside it
+ *   ux, uy = window means of x, c;  vx = cov (E[x^2] - ux^2), vy likewise, vxy = cov (E[x c] - ux uy)
+ *   A1 = 2 ux uy + C1, A2 = 2 vxy + C2, B1 = ux^2 + uy^2 + C1, B2 = vx + vy + C2,   S_w = A1 A2 / (B1 B2)
+ *   SSIM = the mean of S_w over all B C Nw windows;   the term is 1 - SSIM.
+ * Gradient.  Per window  b_w = -2 cov S_w / B2,  c_w = 2 cov A1 / (B1 B2),  d_w = 2 uy A2 / (B1 B2) - 2 ux S_w / B1;  per pixel p
+ *   d SSIM / d y_p = [0 <= y_p <= 1] / (49 B C Nw) * sum over the windows w that hold p of (d_w + b_w (x_p - ux_w) + c_w (c_p - uy_w))
+ *   (bounds of the mask included, as for the other loss terms).  C1, C2 keep every denominator >= C1 C2: a flat or all-zero plane is no
+ *   special case; y == c gives SSIM = 1.  A NaN in y or clean makes both values of `out` NaN; +-inf in y clamps and gets gradient 0.
+ * out: two fp32 values on the device, {(base_loss ? *base_loss : 0) + w_ssim (1 - SSIM), SSIM}, each formed in float64 and rounded once.
+ * grad (optional, fp32, the shape of y): accumulate == 0: grad = g with g = fp32(-w_ssim d SSIM / d y); accumulate == 1: grad = grad + g,
+ *   one fp32 addition per element (the gradient of the base loss is already there).  Every element is written.
+ * base_loss (optional): a device fp32 scalar (the loss the term is added to), read by launch 2.
+ * Arithmetic: window sums, S, the three coefficients and the sums over windows in float64 (E[x^2] - ux^2 cancels in fp32); no multiply-add
+ * is fused.  Launch 1 (a workgroup owns a 16 x 32 tile of one image and walks the bands) writes grad and one float64 partial (sum of S_w
+ * over the windows centred in its tile, all bands) per workgroup to `workspace`; launch 2 (one workgroup) adds them in ascending block
+ * order with a fixed tree and writes `out`.  No atomics, nothing read back, nothing zero-filled: capturable, bitwise equal from run to
+ * run and between rows that start on 16 bytes and rows that do not.  Both launch under the ids of the spectral-loss pair
+ * (MPHSIR_K_SPECTRAL_LOSS / MPHSIR_K_SPECTRAL_LOSS_FINISH), as mphsir_quality_meter launches under MPHSIR_K_QUALITY.
+ * workspace: mphsir_ssim_loss_workspace_bytes(B, C, H, W) bytes, 8-byte aligned, caller-owned (negative: sizes refused).
+ * Refused (MPHSIR_EINVAL, nothing launched): another struct_size; a null y / clean / out / workspace; H < 7 or W < 7; B or C < 1, H W >=
+ * 2^31 or more than 2^31 - 1 workgroups; a weight that is not finite or <= 0; accumulate other than 0 / 1, or 1 without grad; a workspace
+ * that is too small or not 8-byte aligned.                                                                                          */
+struct mphsir_ssim_loss_args {
+    uint32_t struct_size;       /* = sizeof(this struct), set by the caller: any other value is rejected with MPHSIR_EINVAL */
+    const float* y;
+    const float* clean;
+    float* grad;
+    const float* base_loss;
+    float* out;
+    void* workspace;
+    int64_t workspace_bytes;
+    int32_t B, C, H, W;
+    float w_ssim;
+    int32_t accumulate;
+};
+typedef struct mphsir_ssim_loss_args mphsir_ssim_loss_args;
+int64_t mphsir_ssim_loss_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int mphsir_ssim_loss(const mphsir_ssim_loss_args* a, void* stream);
+
 /* ---- optional per-kernel launch timer (bench.py roofline leg) ----------------------------------
  * When enabled for kernel id `kid`, every launch of that kernel is bracketed by hipEvents on its
  * own stream.  read(): synchronises the recorded events, returns the number of launches and their

@@ -208,6 +208,12 @@ class SpectralLossArgs(_Args):
                [(n, c_int32) for n in ("B", "C", "H", "W")] + [("w_sam", ctypes.c_float), ("w_sdiff", ctypes.c_float)]
 
 
+class SsimLossArgs(_Args):
+    """ctypes image of mphsir_ssim_loss_args (a float member: compared with the header by tests/test_ssim_loss_host.py)"""
+    _fields_ = _SZ + [(n, c_void_p) for n in ("y", "clean", "grad", "base_loss", "out", "workspace")] + [("workspace_bytes", c_int64)] + \
+               [(n, c_int32) for n in ("B", "C", "H", "W")] + [("w_ssim", ctypes.c_float), ("accumulate", c_int32)]
+
+
 class TnProblem(ctypes.Structure):
     """mirror of struct mphsir_gemm_tn_problem"""
     _fields_ = [("A", c_void_p), ("lda", c_int64), ("B", c_void_p), ("ldb", c_int64), ("Cpart", c_void_p), ("colsum_part", c_void_p),
@@ -326,6 +332,8 @@ _SYMBOLS = {
     "mphsir_l1_clamp_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
     "mphsir_spectral_loss_workspace_bytes": (c_int64, [c_int32] * 4),
     "mphsir_spectral_loss": (c_int, [ctypes.POINTER(SpectralLossArgs), c_void_p]),
+    "mphsir_ssim_loss_workspace_bytes": (c_int64, [c_int32] * 4),
+    "mphsir_ssim_loss": (c_int, [ctypes.POINTER(SsimLossArgs), c_void_p]),
 }
 
 

@@ -224,3 +224,301 @@ extern "C" int mphsir_pack_gather(const float* arena, const int32_t* index, void
     }
     return MPHSIR_OK;
 }
+
+// ---- ssim_loss: the SSIM term of the training loss, w (1 - SSIM), and its gradient in one launch pair (include/mphsir.h holds the
+// definitions; mp-hsir_amd/ops.py ssim_loss_grad, engine.SpectralLoss(ssim=) the Python side).  The SSIM is the one quality.hip reports.
+//
+//   ssim_loss_kernel          a workgroup owns SSL_TH x SSL_TW = 16 x 32 pixels of one image and walks the bands.  A pixel lies in the 49
+//                             windows centred within 3 of it, and those reach 3 further: per band the workgroup stages its pixels plus a
+//                             6-pixel halo of both cubes (x clipped to [0,1]; fp32 -> fp64 is exact, so the stage is fp32) and then, in
+//                             float64 throughout,
+//                               1. the five 7-wide row sums (x, c, xx, cc, xc) of every staged row at the 38 centre columns,
+//                               2. seven rows of them per window centre (22 x 38 centres: the tile plus 3 around it) -> S_w and the three
+//                                  coefficients a_w = d_w - ux_w b_w - uy_w c_w, b_w, c_w of include/mphsir.h, 0 where the window does not
+//                                  lie inside the plane; S_w of the centres inside the tile is added to the thread's partial,
+//                               3. the 7-wide row sums of the three coefficient maps at the 32 pixel columns,
+//                               4. seven rows of them per pixel: g = scale (sum a + x_p sum b + c_p sum c), scale = -w / (49 B C Nw), rounded
+//                                  to fp32 once, 0 where y_p is outside [0,1], written (or added to what `grad` holds: accumulate).
+//                             The uncentred form (three box sums) loses log2(|terms| / |g|) ~ 10 bits on smooth planes -- of 53.
+//                             The next band's loads are issued before the current band's arithmetic and land in registers meanwhile.
+//                             The coefficient maps share their LDS with the stage (dead once the row sums exist), the second row sums
+//                             with the first: 62.6 KB, two workgroups per CU; four barriers per band.
+//                             After the last band the workgroup's float64 sum of S_w goes to its workspace slot.
+//   ssim_loss_finish_kernel   one workgroup: the partials summed by thread in ascending block order, the lanes by a fixed shuffle tree, the
+//                             four waves in order; writes {base + w (1 - SSIM), SSIM} as fp32, each rounded once.
+//
+// No atomics, nothing zero-filled, no sum whose order depends on scheduling.  Both launch under the kernel ids of the spectral-loss pair
+// (MPHSIR_K_SPECTRAL_LOSS, MPHSIR_K_SPECTRAL_LOSS_FINISH: the loss family of the launch timer), as quality_meter launches under
+// MPHSIR_K_QUALITY: MPHSIR_K_COUNT stays.  One path for every alignment: the loads and stores are per element.
+//
+// Bounds: every global read is at an image coordinate checked against [0,H) x [0,W) (H W < 2^31: the plane offset is an int; positions
+// outside are staged as 0 and only enter windows whose coefficients are replaced by 0 and whose S is not counted); a gradient element is
+// stored only where its pixel is inside the image; LDS indices: stage rows < 28, columns < 44; row sums [5][28][38], a pair of columns
+// 2 i, 2 i + 1 <= 37 reads stage columns <= 44 - 1; coefficient maps [3][22][38], a pair of centre rows 2 i, 2 i + 1 <= 21 reads row sums
+// <= 27; second row sums [3][22][32] read map columns <= 31 + 6; a pixel pair reads their rows <= 15 + 6.  Workspace slot blk < B * tiles
+// lies inside the 8 B tiles bytes the host verified.
+// Aliasing: `mp` is the stage, then the maps; `hs` the first row sums, then the second.  With a gradient a band has four barriers: stage
+// written | B1 | stage read, hs written | B2 | hs read, maps written over the stage | B3 | maps read, hs rewritten | B4 | hs read; the next
+// stage write comes behind B4 (the maps are dead), the next hs write behind the next B1 (step 4 is over).  WITHOUT a gradient (grad == NULL,
+// the same for the whole workgroup) a band has B1 and B2 only and writes neither the maps nor the second row sums: the next stage write
+// follows B2 of the same band (the stage's last readers, step 1 and cp, are in front of B2), the next hs write follows the next B1 (step
+// 2, the last reader of hs, is in front of it).  Anything added behind step 2 on that path that reads `mp` or writes `hs` needs a barrier of
+// its own.
+//
+// No multiply-add is fused from here on (spectral_loss.hip has the reason; the kernels above hold no a * b + c).
+#pragma clang fp contract(off)
+
+namespace mphsir {
+
+constexpr int SSL_TH = 16, SSL_TW = 32, SSL_R = 3, SSL_NT = 256;
+constexpr int SSL_SH = SSL_TH + 4 * SSL_R, SSL_SW = SSL_TW + 4 * SSL_R;         // the stage: 28 x 44
+constexpr int SSL_CH = SSL_TH + 2 * SSL_R, SSL_CW = SSL_TW + 2 * SSL_R;         // window centres a workgroup evaluates: 22 x 38
+constexpr int SSL_LD = (SSL_SH * SSL_SW + SSL_NT - 1) / SSL_NT;                 // staged elements per thread and cube
+constexpr int SSL_RPT = SSL_TH / (SSL_NT / SSL_TW);                             // rows a thread owns in its column
+constexpr int SSL_HS = 5 * SSL_SH * SSL_CW, SSL_MAPS = 3 * SSL_CH * SSL_CW;     // doubles
+static_assert(SSL_RPT == 2 && SSL_CW % 2 == 0 && SSL_CH % 2 == 0 && SSL_TW % 2 == 0 && SSL_R == 3, "pairs of columns / rows share six of their seven samples");
+static_assert(2 * SSL_SH * SSL_SW * 4 <= SSL_MAPS * 8 && 3 * SSL_CH * SSL_TW <= SSL_HS, "the maps lie over the stage, the second row sums over the first");
+static_assert((SSL_HS + SSL_MAPS + 4) * 8 <= 64 * 1024, "static LDS");
+
+struct SsimLossDev {
+    const float* y; const float* c; float* g; double* ws;
+    int C, H, W, tiles_x, tiles;
+    int accumulate;
+    double scale;               // -w / (49 B C Nw)
+};
+
+// the seven-term sums of two neighbouring positions from their eight samples: plain sums, nothing is subtracted
+__device__ __forceinline__ void ssl_pair(const double* v, double& s0, double& s1) {
+    const double core = ((v[1] + v[2]) + (v[3] + v[4])) + (v[5] + v[6]);
+    s0 = v[0] + core;
+    s1 = core + v[7];
+}
+
+// grid (B * tiles): workgroup blk owns tile blk % tiles of image blk / tiles
+__global__ __launch_bounds__(SSL_NT) void ssim_loss_kernel(SsimLossDev a) {
+    __shared__ double hs[SSL_HS];                   // [5][28][38] row sums, later [3][22][32] row sums of the coefficient maps
+    __shared__ double mp[SSL_MAPS];                 // the fp32 stage [2][28][44], later the coefficient maps [3][22][38]
+    __shared__ double red[SSL_NT / 64];
+    float* sx = reinterpret_cast<float*>(mp);
+    float* sc = sx + SSL_SH * SSL_SW;
+
+    const int t = threadIdx.x, lane = t & 63, wave = wave_id_uniform();
+    const int b = blockIdx.x / a.tiles, blk = blockIdx.x - b * a.tiles;
+    const int by = blk / a.tiles_x, bx = blk - by * a.tiles_x;
+    const int y0 = by * SSL_TH, x0 = bx * SSL_TW;
+    const long plane = (long)a.H * a.W;
+    const float* py = a.y + (long)b * a.C * plane;
+    const float* pc = a.c + (long)b * a.C * plane;
+
+    int off[SSL_LD];                                                        // plane offset of staged element t + k * SSL_NT, -1 outside
+#pragma unroll
+    for (int k = 0; k < SSL_LD; ++k) {
+        const int e = t + k * SSL_NT, r = e / SSL_SW, c = e - r * SSL_SW;
+        const int gy = y0 - 2 * SSL_R + r, gx = x0 - 2 * SSL_R + c;
+        off[k] = (e < SSL_SW * SSL_SH && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? gy * a.W + gx : -1;
+    }
+    const int tx = t & (SSL_TW - 1), tg = t / SSL_TW;
+    int own[SSL_RPT];                                                       // plane offset of the thread's own pixels, -1 outside
+#pragma unroll
+    for (int j = 0; j < SSL_RPT; ++j) {
+        const int gy = y0 + tg * SSL_RPT + j, gx = x0 + tx;
+        own[j] = (gy < a.H && gx < a.W) ? gy * a.W + gx : -1;
+    }
+
+    float rx[SSL_LD], rc[SSL_LD], ry[SSL_RPT];
+#pragma unroll
+    for (int k = 0; k < SSL_LD; ++k) {
+        rx[k] = off[k] >= 0 ? py[off[k]] : 0.f;
+        rc[k] = off[k] >= 0 ? pc[off[k]] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < SSL_RPT; ++j) ry[j] = own[j] >= 0 ? py[own[j]] : 0.f;
+
+    double ss = 0.0;
+    for (int c = 0; c < a.C; ++c) {
+#pragma unroll
+        for (int k = 0; k < SSL_LD; ++k) {
+            const int e = t + k * SSL_NT;
+            if (e < SSL_SW * SSL_SH) {
+                sx[e] = clamp01(rx[k]);
+                sc[e] = rc[k];
+            }
+        }
+        float yo[SSL_RPT];                                                  // the raw y of the own pixels of band c: the mask is taken of it
+#pragma unroll
+        for (int j = 0; j < SSL_RPT; ++j) yo[j] = ry[j];
+        if (c + 1 < a.C) {
+            const float* ny = py + (long)(c + 1) * plane;
+            const float* nc = pc + (long)(c + 1) * plane;
+#pragma unroll
+            for (int k = 0; k < SSL_LD; ++k) {
+                rx[k] = off[k] >= 0 ? ny[off[k]] : 0.f;
+                rc[k] = off[k] >= 0 ? nc[off[k]] : 0.f;
+            }
+#pragma unroll
+            for (int j = 0; j < SSL_RPT; ++j) ry[j] = own[j] >= 0 ? ny[own[j]] : 0.f;
+        }
+        __syncthreads();                     // the stage of band c is complete (everyone has left step 4 of band c - 1: see the barrier before it)
+
+        // 1. row sums: staged row r, the windows centred on centre columns col and col + 1
+        for (int e = t; e < SSL_SH * (SSL_CW / 2); e += SSL_NT) {
+            const int r = e / (SSL_CW / 2), col = (e - r * (SSL_CW / 2)) * 2;
+            const float* fx = sx + r * SSL_SW + col;
+            const float* fc = sc + r * SSL_SW + col;
+            double v[5][8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const double xv = fx[k], cv = fc[k];
+                v[0][k] = xv;
+                v[1][k] = cv;
+                v[2][k] = xv * xv;
+                v[3][k] = cv * cv;
+                v[4][k] = xv * cv;
+            }
+#pragma unroll
+            for (int q = 0; q < 5; ++q) {
+                double* o = hs + (q * SSL_SH + r) * SSL_CW + col;
+                ssl_pair(v[q], o[0], o[1]);
+            }
+        }
+        float cp[SSL_RPT];                                                  // clean at the own pixels (0 outside the image)
+#pragma unroll
+        for (int j = 0; j < SSL_RPT; ++j) cp[j] = sc[(tg * SSL_RPT + j + 2 * SSL_R) * SSL_SW + tx + 2 * SSL_R];
+        __syncthreads();                     // the row sums are complete; nobody reads the stage any more: the maps may overwrite it
+
+        // 2. windows: centre rows 2 rp, 2 rp + 1 at centre column j -> S and the three coefficients
+        for (int e = t; e < (SSL_CH / 2) * SSL_CW; e += SSL_NT) {
+            const int rp = e / SSL_CW, j = e - rp * SSL_CW;
+            double S[5][2];
+#pragma unroll
+            for (int q = 0; q < 5; ++q) {
+                double v[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = hs[(q * SSL_SH + 2 * rp + k) * SSL_CW + j];
+                ssl_pair(v, S[q][0], S[q][1]);
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int ci = 2 * rp + i, gy = y0 - SSL_R + ci, gx = x0 - SSL_R + j;
+                const bool valid = gy >= SSL_R && gy < a.H - SSL_R && gx >= SSL_R && gx < a.W - SSL_R;
+                const bool mine = ci >= SSL_R && ci < SSL_R + SSL_TH && j >= SSL_R && j < SSL_R + SSL_TW;
+                const double inv = 1.0 / 49.0, cov = 49.0 / 48.0, c1 = 1e-4, c2 = 9e-4;
+                const double ux = S[0][i] * inv, uy = S[1][i] * inv;
+                const double vx = cov * (S[2][i] * inv - ux * ux), vy = cov * (S[3][i] * inv - uy * uy), vxy = cov * (S[4][i] * inv - ux * uy);
+                const double A1 = 2.0 * ux * uy + c1, A2 = 2.0 * vxy + c2, B1 = ux * ux + uy * uy + c1, B2 = vx + vy + c2;
+                const double den = B1 * B2, s = (A1 * A2) / den;
+                if (valid && mine) ss += s;
+                if (a.g != nullptr) {
+                    const double rden = 1.0 / den;
+                    const double bw = -2.0 * cov * s * (B1 * rden), cw = 2.0 * cov * A1 * rden;
+                    const double dw = 2.0 * uy * A2 * rden - 2.0 * ux * s * (B2 * rden);
+                    const double aw = (dw - ux * bw) - uy * cw;
+                    double* o = mp + ci * SSL_CW + j;
+                    o[0] = valid ? aw : 0.0;
+                    o[SSL_CH * SSL_CW] = valid ? bw : 0.0;
+                    o[2 * SSL_CH * SSL_CW] = valid ? cw : 0.0;
+                }
+            }
+        }
+        if (a.g == nullptr) continue;        // the value alone (the same for every thread): the next stage is read by nobody now, and the
+                                             // next row sums are written behind the next band's first barrier, after step 2's readers
+        __syncthreads();                   // the maps are complete; nobody reads the first row sums any more
+
+        // 3. row sums of the maps: centre row r, the pixels of tile columns col and col + 1
+        for (int e = t; e < SSL_CH * (SSL_TW / 2); e += SSL_NT) {
+            const int r = e / (SSL_TW / 2), col = (e - r * (SSL_TW / 2)) * 2;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const double* m = mp + (q * SSL_CH + r) * SSL_CW + col;
+                double v[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = m[k];
+                double* o = hs + (q * SSL_CH + r) * SSL_TW + col;
+                ssl_pair(v, o[0], o[1]);
+            }
+        }
+        __syncthreads();                     // the second row sums are complete; nobody reads the maps any more: the next stage may overwrite them
+
+        // 4. the gradient of the thread's two pixels
+        double G[3][2];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            double v[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = hs[(q * SSL_CH + tg * SSL_RPT + k) * SSL_TW + tx];
+            ssl_pair(v, G[q][0], G[q][1]);
+        }
+        float* pg = a.g + ((long)b * a.C + c) * plane;
+#pragma unroll
+        for (int j = 0; j < SSL_RPT; ++j) {
+            if (own[j] < 0) continue;
+            const double xv = clamp01(yo[j]), cv = cp[j];
+            const double sum = (G[0][j] + xv * G[1][j]) + cv * G[2][j];
+            const float g = (yo[j] >= 0.f && yo[j] <= 1.f) ? (float)(a.scale * sum) : 0.f;
+            pg[own[j]] = a.accumulate ? pg[own[j]] + g : g;
+        }
+    }
+    ss = wave_sum(ss);
+    if (lane == 0) red[wave] = ss;
+    __syncthreads();
+    if (t == 0) a.ws[blockIdx.x] = sum4_ordered(red, 1);
+}
+
+struct SsimLossFinishDev {
+    const double* ws; const float* base; float* out;
+    long nblk;
+    double count, w;            // B C Nw, the weight
+};
+
+__global__ __launch_bounds__(SSL_NT) void ssim_loss_finish_kernel(SsimLossFinishDev a) {
+    __shared__ double red[SSL_NT / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = wave_id_uniform();
+    double s = 0.0;
+    for (long i = t; i < a.nblk; i += SSL_NT) s += a.ws[i];
+    s = wave_sum(s);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    if (t != 0) return;
+    const double ssim = sum4_ordered(red, 1) / a.count;
+    const double base = a.base != nullptr ? (double)a.base[0] : 0.0;
+    a.out[0] = (float)(base + a.w * (1.0 - ssim));
+    a.out[1] = (float)ssim;
+}
+
+static long ssim_loss_blocks(int B, int C, int H, int W) {              // 0: sizes refused
+    if (B < 1 || C < 1 || H < 2 * SSL_R + 1 || W < 2 * SSL_R + 1 || (long)H * W >= (1L << 31)) return 0;
+    const long tiles = (long)((H + SSL_TH - 1) / SSL_TH) * ((W + SSL_TW - 1) / SSL_TW);
+    return tiles * B < (1L << 31) ? tiles * B : 0;
+}
+
+}  // namespace mphsir
+
+extern "C" int64_t mphsir_ssim_loss_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
+    const long n = mphsir::ssim_loss_blocks(B, C, H, W);
+    return n ? (int64_t)8 * n : MPHSIR_EINVAL;
+}
+
+extern "C" int mphsir_ssim_loss(const mphsir_ssim_loss_args* a, void* stream) {
+    using namespace mphsir;
+    clear_error();
+    MPHSIR_CHECK_ARGS(a, "ssim_loss");
+    MPHSIR_REQUIRE(a->y && a->clean && a->out && a->workspace, "ssim_loss: null pointer");
+    MPHSIR_REQUIRE(a->H >= 2 * SSL_R + 1 && a->W >= 2 * SSL_R + 1, "ssim_loss: a band of %d x %d holds no 7 x 7 window", a->H, a->W);
+    const long nblk = ssim_loss_blocks(a->B, a->C, a->H, a->W);
+    MPHSIR_REQUIRE(nblk > 0, "ssim_loss: bad sizes (B %d, C %d, H %d, W %d: B, C >= 1, H * W < 2^31, at most 2^31 - 1 workgroups of 16 x 32 pixels)",
+                   a->B, a->C, a->H, a->W);
+    MPHSIR_REQUIRE(a->w_ssim > 0.f && a->w_ssim <= 3.4e38f, "ssim_loss: the weight must be finite and > 0 (w_ssim %g)", (double)a->w_ssim);
+    MPHSIR_REQUIRE(a->accumulate == 0 || (a->accumulate == 1 && a->grad != nullptr),
+                   "ssim_loss: accumulate must be 0 or 1, and 1 needs a grad to add to (accumulate %d)", a->accumulate);
+    MPHSIR_REQUIRE(a->workspace_bytes >= 8 * nblk && (reinterpret_cast<uintptr_t>(a->workspace) & 7) == 0,
+                   "ssim_loss: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)a->workspace_bytes, (long long)(8 * nblk));
+    const int tiles_x = (a->W + SSL_TW - 1) / SSL_TW;
+    const double count = (double)a->B * (double)a->C * (double)(a->H - 2 * SSL_R) * (double)(a->W - 2 * SSL_R);
+    SsimLossDev d{a->y, a->clean, a->grad, static_cast<double*>(a->workspace), a->C, a->H, a->W, tiles_x, (int)(nblk / a->B), a->accumulate,
+                  -(double)a->w_ssim / (49.0 * count)};
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    MPHSIR_LAUNCH(MPHSIR_K_SPECTRAL_LOSS, ssim_loss_kernel, dim3((unsigned)nblk), dim3(SSL_NT), 0, s, d);
+    SsimLossFinishDev f{static_cast<const double*>(a->workspace), a->base_loss, a->out, nblk, count, (double)a->w_ssim};
+    MPHSIR_LAUNCH(MPHSIR_K_SPECTRAL_LOSS_FINISH, ssim_loss_finish_kernel, dim3(1), dim3(SSL_NT), 0, s, f);
+    return MPHSIR_OK;
+}

@@ -35,19 +35,33 @@ def l1_after_clamp(restored, clean):
 class SpectralLoss:
     """loss_fn with spectral terms: l1_after_clamp + sam * (mean spectral angle, radians) + sdiff * (L1 of band-to-band differences), one
     launch pair for the loss and its gradient (ops.spectral_loss; the definitions: include/mphsir.h).  Off unless handed to the engine:
-    `DataParallelEngine(net, lr, loss_fn=SpectralLoss(sam=0.1))`."""
+    `DataParallelEngine(net, lr, loss_fn=SpectralLoss(sam=0.1))`.
 
-    def __init__(self, sam=0.0, sdiff=0.0):
-        sam, sdiff = float(sam), float(sdiff)
-        assert 0.0 <= sam < float("inf") and 0.0 <= sdiff < float("inf"), "SpectralLoss: weights must be finite and >= 0, got %r / %r" % (sam, sdiff)
-        assert sam > 0.0 or sdiff > 0.0, "SpectralLoss: both weights are 0 -- that loss is l1_after_clamp"
-        self.sam, self.sdiff = sam, sdiff
+    ssim > 0 adds ssim * (1 - SSIM), the band-wise 7 x 7 SSIM that metrics.ssim_bands / ops.quality_bands report, by a launch pair of its own
+    (ops.ssim_loss) behind the base loss: the spectral pair when sam or sdiff > 0, else l1_after_clamp's launch."""
+
+    def __init__(self, sam=0.0, sdiff=0.0, ssim=0.0):
+        sam, sdiff, ssim = float(sam), float(sdiff), float(ssim)
+        assert 0.0 <= sam < float("inf") and 0.0 <= sdiff < float("inf") and 0.0 <= ssim < float("inf"), \
+            "SpectralLoss: weights must be finite and >= 0, got %r / %r / %r" % (sam, sdiff, ssim)
+        assert sam > 0.0 or sdiff > 0.0 or ssim > 0.0, "SpectralLoss: all weights are 0 -- that loss is l1_after_clamp"
+        self.sam, self.sdiff, self.ssim = sam, sdiff, ssim
+
+    @property
+    def spectral(self):
+        """the base loss is the spectral launch pair (else l1_after_clamp's launch)"""
+        return self.sam > 0.0 or self.sdiff > 0.0
 
     def __call__(self, restored, clean):
-        return ops.spectral_loss(restored.float(), clean.float(), self.sam, self.sdiff)
+        restored, clean = restored.float(), clean.float()
+        loss = ops.spectral_loss(restored, clean, self.sam, self.sdiff) if self.spectral else ops.l1_clamp_loss(restored, clean)
+        return loss + ops.ssim_loss(restored, clean, self.ssim) if self.ssim > 0.0 else loss
 
     def weights(self):
-        return {"sam": self.sam, "sdiff": self.sdiff}
+        w = {"sam": self.sam, "sdiff": self.sdiff}
+        if self.ssim > 0.0:
+            w["ssim"] = self.ssim
+        return w
 
 
 class PackPlan:
@@ -234,6 +248,7 @@ class DataParallelEngine:
         self.grad_clip, self.ema_decay, self.ema_warmup = grad_clip, ema_decay, ema_warmup
         self.flat_ema = self.optim_stats = self._gn_ws = None
         self._loss_parts = None         # SpectralLoss: the device fp32[4] {loss, L1, SAM, SDIFF} of the last step (graph mode: the replayed buffer)
+        self._ssim_parts = self._base_loss = None   # SpectralLoss(ssim > 0): the device fp32[2] {loss, SSIM} and the base scalar it was added to
         # An eager step of the default loss hands the optimizer kernel lr and the step number, and the library forms Adam's bias corrections
         # with fp32 powf; a replayed step reads [lr, 1 - beta1^t, sqrt(1 - beta2^t)] that the host formed in float64 (1 - 0.9f = 0.100000024
         # against fp32(1 - 0.9) = 0.1 at t = 1): eager and graph mode differ in the last bits from the first replayed step on.  That is what
@@ -392,10 +407,15 @@ class DataParallelEngine:
         spectral = isinstance(self.loss_fn, SpectralLoss)
         if ((spectral or self.loss_fn is l1_after_clamp) and restored.dtype == torch.float32 and clean.dtype == torch.float32
                 and restored.shape == clean.shape and restored.requires_grad and (not spectral or restored.dim() == 4)):
-            if spectral:
+            if spectral and self.loss_fn.spectral:
                 loss, g, self._loss_parts = ops.spectral_loss_grad(restored.detach(), clean, self.loss_fn.sam, self.loss_fn.sdiff)
             else:
                 loss, g = ops.l1_clamp_loss_grad(restored.detach(), clean)
+            if spectral and self.loss_fn.ssim > 0.0:
+                # the SSIM pair follows on the same stream: its gradient is added to the base loss's in place, its second launch adds the
+                # base scalar -- the backward pass starts from the summed gradient exactly as it does from the base loss's alone
+                self._base_loss = loss.reshape(1)
+                loss, g, self._ssim_parts = ops.ssim_loss_grad(restored.detach(), clean, self.loss_fn.ssim, base_loss=self._base_loss, grad=g)
             if self._use_scaler(restored.device):
                 g.mul_(self.scaler[0])
             with ops.deferred_reductions():
@@ -607,10 +627,21 @@ class DataParallelEngine:
 
     def loss_components(self):
         """{'loss', 'l1', 'sam_deg', 'sdiff'} of the last step under a SpectralLoss (None under any other loss, or before the first
-        step): the unweighted terms, the spectral angle in degrees.  ONE device-to-host transfer: call it when logging, not every step."""
+        step): the unweighted terms, the spectral angle in degrees; with the SSIM term on also 'ssim', the SSIM itself.  ONE device-to-host
+        transfer: call it when logging, not every step."""
+        import math
+        # _ssim_parts, like _loss_parts, is set by the fast path of _loss_backward and never cleared: a later step that leaves that path
+        # (a `restored` that is not 4-D fp32, say) leaves the values of the last step that took it -- the behaviour the spectral terms have
+        if self._ssim_parts is not None:
+            # with the SSIM term: 'loss' is the whole loss, 'ssim' the SSIM itself (not 1 - SSIM); without spectral terms the base scalar is L1
+            if self._loss_parts is not None:
+                v = torch.cat([self._loss_parts.detach(), self._ssim_parts.detach()]).cpu().tolist()
+            else:
+                v = torch.cat([self._base_loss.detach(), self._ssim_parts.detach()]).cpu().tolist()
+                v = [v[0], v[0], 0.0, 0.0, v[1], v[2]]
+            return {"loss": v[4], "l1": v[1], "sam_deg": math.degrees(v[2]), "sdiff": v[3], "ssim": v[5]}
         if self._loss_parts is None:
             return None
-        import math
         v = self._loss_parts.detach().cpu().tolist()
         return {"loss": v[0], "l1": v[1], "sam_deg": math.degrees(v[2]), "sdiff": v[3]}
 

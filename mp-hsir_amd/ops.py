@@ -586,6 +586,79 @@ def spectral_loss_grad(y, clean, w_sam, w_sdiff):
     return out[0], g, out
 
 
+_SSIM_WS = {}          # (device, stream, bytes) -> the float64 block partials of mphsir_ssim_loss, reused from call to call
+
+
+def ssim_loss_workspace(y):
+    """the workspace mphsir_ssim_loss needs for a (B,C,H,W) cube like y, one per (device, stream, size): launch 2 has consumed it when
+    the call returns to the stream, so the next call on that stream may overwrite it"""
+    B, C, H, W = y.shape
+    nbytes = _workspace_bytes("ssim_loss", "ssim_loss refuses (B %d, C %d, H %d, W %d: H, W >= 7)", B, C, H, W)
+    key = (y.device, torch.cuda.current_stream(y.device).cuda_stream if y.is_cuda else 0, nbytes)
+    ws = _SSIM_WS.get(key)
+    if ws is None:
+        ws = _SSIM_WS[key] = torch.empty((nbytes // 8,), dtype=torch.float64, device=y.device)
+    return ws
+
+
+def _ssim_loss_launch(y, clean, w_ssim, base_loss, grad, want_grad):
+    """one launch pair: -> (fp32[2] {base + w_ssim (1 - SSIM), SSIM} on the device, the gradient buffer or None); include/mphsir.h holds
+    the definition.  grad given: the term's gradient is ADDED to it (accumulate), one fp32 addition per element"""
+    lib = _lib.load()
+    _check(y, clean, base_loss, grad)
+    assert y.dtype == torch.float32 and clean.dtype == torch.float32, "ssim_loss: fp32 inputs, got %s / %s" % (y.dtype, clean.dtype)
+    assert y.dim() == 4 and y.shape == clean.shape and y.device == clean.device, "ssim_loss: two (B,C,H,W) cubes of one shape on one device"
+    w_ssim = float(w_ssim)
+    if not 0.0 < w_ssim < float("inf"):
+        raise RuntimeError("mp-hsir_amd: ssim_loss: the weight must be finite and > 0, got %r" % (w_ssim,))
+    if base_loss is not None:
+        assert base_loss.dtype == torch.float32 and base_loss.numel() == 1 and base_loss.device == y.device, "ssim_loss: base_loss is one fp32 value on y's device"
+    if grad is not None:
+        assert grad.dtype == torch.float32 and grad.shape == y.shape and grad.device == y.device and grad.is_contiguous(), \
+            "ssim_loss: grad is a contiguous fp32 tensor of y's shape on y's device"
+    y, clean = y.contiguous(), clean.contiguous()
+    B, C, H, W = y.shape
+    ws = ssim_loss_workspace(y)
+    g = grad if grad is not None else (torch.empty_like(y) if want_grad else None)
+    out = torch.empty((2,), dtype=torch.float32, device=y.device)
+    a = _lib.SsimLossArgs(y=_p(y), clean=_p(clean), grad=_p(g), base_loss=_p(base_loss), out=_p(out), workspace=_p(ws),
+                          workspace_bytes=8 * ws.numel(), B=B, C=C, H=H, W=W, w_ssim=w_ssim, accumulate=1 if grad is not None else 0)
+    _lib.check(lib.mphsir_ssim_loss(ctypes.byref(a), _stream(y)), "ssim_loss")
+    n = float(y.numel())
+    # per pixel and band: 1.63 windows of ~110 float64 operations (five row sums, five column sums, S and the coefficients) and ~45 for the
+    # three box sums and the gradient; both cubes read once plus the halo, grad written (accumulate: read as well)
+    _acct("ssim_loss", 225.0 * n, 4.0 * n * (2 + (0 if g is None else (2 if grad is not None else 1))))
+    return out, g
+
+
+class _SsimLoss(torch.autograd.Function):
+    """w_ssim (1 - SSIM) of clamp(y, 0, 1) against clean with its gradient from the same launch (mphsir_ssim_loss)"""
+
+    @staticmethod
+    def forward(ctx, y, clean, w_ssim):
+        out, ctx.g = _ssim_loss_launch(y, clean, w_ssim, None, None, ctx.needs_input_grad[0])
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        g, ctx.g = ctx.g, None
+        assert g is not None, "ssim_loss: its gradient buffer is scaled in place and handed over: backward() runs once"
+        return g.mul_(dloss), None, None
+
+
+def ssim_loss(y, clean, w_ssim):
+    """the SSIM term w_ssim (1 - SSIM) as a 0-d tensor, differentiable w.r.t. y"""
+    return _SsimLoss.apply(y, clean, w_ssim)
+
+
+def ssim_loss_grad(y, clean, w_ssim, base_loss=None, grad=None):
+    """(loss, gradient, out = fp32[2] {loss, SSIM}) from one launch pair, outside autograd.  loss = w_ssim (1 - SSIM), plus the device
+    scalar base_loss when given; grad given (the gradient of the base loss w.r.t. y): the term's gradient is added to it in place and it
+    is returned, else a new tensor holds the term's gradient alone"""
+    out, g = _ssim_loss_launch(y, clean, w_ssim, base_loss, grad, True)
+    return out[0], g, out
+
+
 def _rows(t):
     """(rows, ld) of a 2-D view whose last dim is contiguous."""
     assert t.dim() == 2 and t.stride(1) == 1, "expected a row-major 2-D view"

@@ -6,7 +6,7 @@ options.py (options.py:6-37), so its command lines (README.md:36,38) work unchan
 Like the reference, the namespace is built at import time (`from options import options as opt`);
 unknown flags are tolerated so that importing this module under pytest/torchrun does not abort.
 Additions (not present in the reference, all optional): --model, --precision, --steps_per_epoch, --graph,
---synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade, --scene_dir, --crop_jitter, --grad_clip, --ema_decay, --task_classes, --cassi_mask, --cassi_step, --loss_sam, --loss_sdiff, --val_dir, --val_every, --val_patch, --val_crops, --val_batch, --val_modes, --val_seed, --val_weights,
+--synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade, --scene_dir, --crop_jitter, --grad_clip, --ema_decay, --task_classes, --cassi_mask, --cassi_step, --loss_sam, --loss_sdiff, --loss_ssim, --val_dir, --val_every, --val_patch, --val_crops, --val_batch, --val_modes, --val_seed, --val_weights,
 --save_best.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
 into ['0','1'] (options.py:36) and `--classifier type=bool` treats any non-empty string as True.
 --fused_degrade 1 works at every --patch_size: a patch of up to 128 x 128 is degraded by the plane form of the launch, a larger one (256
@@ -72,6 +72,8 @@ _FLAGS = [
     ("--loss_sam", dict(type=float, default=0.0, help="> 0: add this weight times the mean spectral angle (radians) of the restored patch against the "
                         "clean one to the clamp + L1 loss (engine.SpectralLoss, one fused launch pair); 0 (default): off")),
     ("--loss_sdiff", dict(type=float, default=0.0, help="> 0: add this weight times the L1 of the band-to-band differences; 0 (default): off")),
+    ("--loss_ssim", dict(type=float, default=0.0, help="> 0: add this weight times (1 - SSIM), the band-wise 7 x 7 SSIM that test.py and the in-training "
+                         "validation report (one more fused launch pair; patches of at least 7 x 7); 0 (default): off")),
     # in-training validation (validate.py); --val_every 0 (default): off, the run does what it always did
     ("--val_dir", dict(type=str, default="", help="directory of held-out .mat / .npy cubes")),
     ("--val_every", dict(type=int, default=0, help="0 (default): no validation; E: score the held-out set after every E-th epoch and after the last")),

@@ -18,7 +18,8 @@ count and the CLIP text-embedding table the model was built with.  --ckpt_path i
 key and shape match, epoch 0); --resume 1 additionally restores the optimizer state and continues at the saved epoch + 1.
 --loss_sam F / --loss_sdiff F (both 0 by default: the reference's loss) add the mean spectral angle and the L1 of band-to-band
 differences to the loss (engine.SpectralLoss); the log line then ends with the unweighted terms, checkpoints carry the weights as
-`mphsir_loss` and --resume 1 says so when the run's weights differ from the file's.
+`mphsir_loss` and --resume 1 says so when the run's weights differ from the file's.  --loss_ssim F (0 by default) adds F * (1 - SSIM), the
+band-wise 7 x 7 SSIM the evaluation reports, by a launch pair of its own; the log line then also ends with ` ssim S`.
 --val_every E --val_dir DIR (0 by default: off) scores held-out crops after every E-th epoch and after the last (validate.py: the crops and
 their degraded forms of test.py's modes stay on the device, a pass reads back one small table); rank 0 prints `val epoch E mode M psnr ..
 ssim .. sam .. n ..` per mode and `val epoch E mean ...`, --save_best 1 writes <ckpt_dir>/best.ckpt whenever the mean PSNR improves, and
@@ -87,13 +88,15 @@ def load_warm_start(net, path, device, engine=None, resume=False):
         resume_epoch = int(ckpt.get("epoch", -1)) + 1
         was, now = ckpt.get("mphsir_loss") or {"sam": 0.0, "sdiff": 0.0}, loss_weights(engine)
         if was != now:
-            print("note: the checkpoint was trained with loss weights sam %g sdiff %g, this run continues with sam %g sdiff %g"
-                  % (was["sam"], was["sdiff"], now["sam"], now["sdiff"]), flush=True)
+            named = "ssim" in was or "ssim" in now                    # the SSIM weight is named only when either side has one
+            said = ["sam %g sdiff %g" % (w["sam"], w["sdiff"]) + (" ssim %g" % w.get("ssim", 0.0) if named else "") for w in (was, now)]
+            print("note: the checkpoint was trained with loss weights %s, this run continues with %s" % tuple(said), flush=True)
     return len(kept), resume_epoch
 
 
 def loss_weights(engine):
-    """the weights of the spectral terms of the engine's loss ({"sam": 0, "sdiff": 0}: the reference's clamp + L1)"""
+    """the weights of the spectral terms of the engine's loss ({"sam": 0, "sdiff": 0}: the reference's clamp + L1), and "ssim" when the
+    SSIM term is on"""
     fn = getattr(engine, "loss_fn", None)
     return fn.weights() if isinstance(fn, SpectralLoss) else {"sam": 0.0, "sdiff": 0.0}
 
@@ -154,12 +157,12 @@ def main():
     dtypes = {"bf16": torch.bfloat16, "f32": torch.float32, "f16": torch.float16}
     net = MP_HSIR_Net(**cfg, clip_prompt=clip_prompt, compute_dtype=dtypes[opt.precision]).to(dev).train()
     extras = opt.grad_clip > 0 or opt.ema_decay > 0
-    if opt.loss_sam < 0 or opt.loss_sdiff < 0:
-        raise SystemExit("--loss_sam / --loss_sdiff must be >= 0 (0: the term is off)")
-    spectral = opt.loss_sam > 0 or opt.loss_sdiff > 0          # off: the engine's default loss, the launches and the log lines of always
+    if opt.loss_sam < 0 or opt.loss_sdiff < 0 or opt.loss_ssim < 0:
+        raise SystemExit("--loss_sam / --loss_sdiff / --loss_ssim must be >= 0 (0: the term is off)")
+    spectral = opt.loss_sam > 0 or opt.loss_sdiff > 0 or opt.loss_ssim > 0      # off: the engine's default loss, the launches and the log lines of always
     eng = DataParallelEngine(net, lr=opt.lr, use_graph=bool(opt.graph), grad_clip=opt.grad_clip if opt.grad_clip > 0 else (float("inf") if extras else None),     # EMA alone: measure the norm for the log
                              ema_decay=opt.ema_decay if opt.ema_decay > 0 else None,
-                             **(dict(loss_fn=SpectralLoss(opt.loss_sam, opt.loss_sdiff)) if spectral else {}))
+                             **(dict(loss_fn=SpectralLoss(opt.loss_sam, opt.loss_sdiff, opt.loss_ssim)) if spectral else {}))
     validator = history = None
     if opt.val_every:               # 0 (default): nothing of validate.py is imported or built
         validator, history = build_validation(opt, net, eng, opt.model or opt.data_type, dev)
@@ -232,6 +235,8 @@ def main():
                 if rank == 0 and spectral:          # one more small read-back per logged step: this rank's unweighted terms
                     lc = eng.loss_components()
                     parts = " l1 %.5f sam_deg %.4f sdiff %.5f" % (lc["l1"], lc["sam_deg"], lc["sdiff"])
+                    if "ssim" in lc:
+                        parts += " ssim %.4f" % lc["ssim"]
                 if rank == 0 and extras:
                     gst = eng.grad_stats()          # one small read-back per logged step (the norm is the unclipped one)
                     print("epoch %d it %d lr %.3e grad_norm %.4f clip %.3f train_loss %.5f%s" % (epoch, it + 1, lr, gst["norm"], gst["coef"], running, parts), flush=True)
