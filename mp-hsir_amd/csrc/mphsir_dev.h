@@ -279,8 +279,11 @@ template <> struct Math<float> {
 template <> struct Math<bf16_t> {
     static __device__ __forceinline__ float exp(float x) { return __expf(x); }
     // GELU(x) and GELU'(x) = Phi(x) + x phi(x) for the backward kernels, both as polynomials in xc = clamp(x, -4, 4) like the forward
-    // form below (Phi: the same coefficients; GELU' - 1/2: odd, degree 17, |error| <= 5.5e-5 inside the clamp, <= 5.8e-4 in the tail
-    // below -4 where the exact value runs from -5e-4 to 0) -- no rcp / exp, every fma packs two elements.  (Until round 4: erf by
+    // form below (Phi: the same coefficients; GELU' - 1/2: odd, degree 17; the polynomial's |error| <= 7.0e-5 inside the clamp -- a ripple of
+    // 5.52e-5 up to |x| = 2.7 that grows to 6.2e-5 at 3.77 and 6.95e-5 at |x| = 4; this comment said 5.5e-5 until tests/test_devmath_*.py
+    // measured it -- and <= 5.8e-4 in the tails beyond +-4, where the exact value runs from -5e-4 to 0 and from 1 + 5e-4 to 1.  The fp32 Horner
+    // evaluation adds rounding on top: the terms of Q reach 68 at u = 16 against a sum of 0.13, up to 1.1e-5 seen, 3.0e-5 by the running error
+    // bound of tests/devmath_ref.py) -- no rcp / exp, every fma packs two elements.  (Until round 4: erf by
     // Abramowitz-Stegun 7.1.26 with the hardware exp2 / rcp, ~17 VALU slots + two quarter-rate ones per element.)
     static __device__ __forceinline__ void gelu_pair(float x, float& g, float& dg) {
         const float xc = __builtin_amdgcn_fmed3f(x, -4.0f, 4.0f), u = xc * xc;
@@ -307,8 +310,10 @@ template <> struct Math<bf16_t> {
     // wave and 32-wide hidden chunk ~150 VALU slots against 24 MFMAs, a third of them the quarter-rate rcp / exp of the form above,
     // 88 % of a SIMD's issue cycles taken).  Phi(x) = 1/2 + xc P(xc^2), xc = clamp(x, -4, 4), P an even polynomial of degree 14
     // (minimax fit of the odd part of Phi on [0, 4] in x/4; the power-of-two scale is folded into the coefficients exactly):
-    // |Phi - exact| <= 5.5e-5 everywhere (fp32 evaluation, 4e6 points on [-12, 12]; the tail beyond the clamp is 3.2e-5), i.e.
-    // |GELU - exact| <= 5.5e-5 |x| for x > -4 and <= 2.2e-4 below -- under the rounding step of the 16-bit value it is stored as.
+    // the polynomial's |Phi - exact| <= 5.5e-5 everywhere (5.45e-5, reached beyond the clamp where Phi stays at its value at 4), i.e.
+    // |GELU - exact| <= 5.5e-5 |x| for x > -4 and <= 2.2e-4 below -- under the rounding step of the 16-bit value it is stored as.  The fp32
+    // evaluation adds up to 6e-7 (2.4e-6 by the running error bound): 5.51e-5 and 2.203e-4 are its measured maxima, which this comment
+    // used to quote, rounded, as the bounds.  tests/test_devmath_*.py assert all of this on the device; coefficients: tests/devmath_ref.py.
     // Every operation packs two elements per instruction (v_pk_fma_f32) except the clamp and the max.
     static __device__ __forceinline__ float gelu(float x) {
         const float xc = __builtin_amdgcn_fmed3f(x, -4.0f, 4.0f), u = xc * xc;

@@ -397,6 +397,38 @@ def test_win_attn_single_window(dtype, man, prefix, heads, shift, shape, manifes
     K.check_win_attn("cpu", dtype, man, prefix, heads, shift, shape, manifest)
 
 
+# ---- the checks off the unit Gaussian (kernel_checks.INPUT_PROFILES): row offsets, flat and constant rows, outliers, GELU gain, peaked
+# softmaxes; every bar is max(the check's tolerance, 3 x torch's own error in the compute dtype), printed with the measured error ----
+_PROFILE = K.profile_params(emulator=True)
+
+
+@pytest.mark.parametrize("fn,a,kw,dt,prof", [e[1:] for e in _PROFILE], ids=[e[0] for e in _PROFILE])
+def test_input_profiles(fn, a, kw, dt, prof):
+    K.run_profile("cpu", fn, a, kw, dt, prof)
+
+
+@pytest.mark.parametrize("prof", K.WIN_PROFILES)
+@pytest.mark.parametrize("dtype", [torch.float32])
+@pytest.mark.parametrize("man,prefix,heads,shift,shape", K.WIN_PROFILE_CASES)
+def test_win_attn_input_profiles(dtype, man, prefix, heads, shift, shape, prof, manifest):
+    K.check_win_attn("cpu", dtype, man, prefix, heads, shift, shape, manifest, inputs=prof)
+
+
+@pytest.mark.parametrize("dtype", K.WIN_SATURATED_DTYPES)
+@pytest.mark.parametrize("man,prefix,heads,shift,shape", K.WIN_PROFILE_CASES)
+def test_win_attn_saturated_softmax(dtype, man, prefix, heads, shift, shape, manifest):
+    """logits up to +-95: past the 88.7 where exp overflows fp32, so the softmax stands on its max-subtraction"""
+    K.check_win_attn("cpu", dtype, man, prefix, heads, shift, shape, manifest, inputs="saturated")
+
+
+def test_input_profiles_report():
+    """the table of the run: per check, profile, dtype and tensor the yardstick, the bar and the measured error of the worst case"""
+    K.check_layernorm_tok("cpu", torch.float32, M=63, C=20, inputs="offset")
+    yard, bar, measured = K.PROFILE_STATS[("check_layernorm_tok", "offset", "float32", "y")]
+    assert 0 < yard < bar and 0 < measured < bar and bar <= K.YARD_CAP * K.TOL[torch.float32], (yard, bar, measured)
+    print("\n".join(K.profile_report()))
+
+
 def test_guard_was_active():
     """the checks above ran under tests/guard.py: a check allocates through it and the counters move"""
     import guard
