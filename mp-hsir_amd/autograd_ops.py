@@ -187,7 +187,7 @@ def _pass_a(x2, wqkv, w9, B, H, W, C, heads, ln=None, keep=False):
     (csrc/spectral_fused.hip) where the shape is covered, else the 1x1 GEMM + the depthwise / Gram kernel.  keep (training): t = qkv(LN(x2))
     (M,3C) and q | k after the depthwise conv (M,2C: cheaper to keep than to recompute; None where the two-kernel path cannot emit it)
     are returned for the backward, else both are None."""
-    if (ops.FUSED_TRAIN or not keep) and ops.qkv_dwconv_gram_fits(C, heads, H, W, x2.dtype):
+    if ops.qkv_dwconv_gram_fits(C, heads, H, W, x2.dtype):
         v, gp, sp, _, *kept = ops.qkv_dwconv_gram(x2, wqkv, w9, B, H, W, C, heads, ln=ln, keep=keep)       # keep: ..., t, qk
     else:
         t = ops.gemm_tok(x2, wqkv, ln=ln)

@@ -19,7 +19,6 @@ Re-expresses what the reference gets implicitly from pytorch-lightning (train.py
     skips them too (grad is None), so no weight decay is applied to them.
 """
 import contextlib
-import os
 import torch
 import torch.distributed as dist
 
@@ -228,9 +227,6 @@ class DataParallelEngine:
         # arena-wide reduction after the replay: 58 MB over xGMI is <1 ms next to a ~45 ms step).
         self.use_graph, self.graph_warmup, self._graph, self._graph_key = use_graph, graph_warmup, None, None
         self.use_pack_plan, self.plan = use_pack_plan, None
-        import os
-        # graph mode, world > 1: bucket all-reduces start while the replay is still running (MPHSIR_GRAPH_OVERLAP=0: off)
-        self.graph_overlap = os.environ.get("MPHSIR_GRAPH_OVERLAP", "1") != "0"
         self.force_eager = False        # diagnostics: run a graph-mode engine's step with eager launches (same data flow)
         # fp16 compute (the reference's precision="16-mixed", train.py:118) needs dynamic loss scaling: the loss is
         # multiplied by a device-resident scale before backward, the optimizer kernel divides it out again and skips
@@ -325,7 +321,8 @@ class DataParallelEngine:
                 bucket_of[p] = bi
             self._remaining = [b[2] for b in self.buckets]
             self._capturing, self._bucket_order = False, []
-            self._overlap = self.use_graph and self.graph_overlap and _external_events_work(dev)
+            # graph mode, world > 1: bucket all-reduces start while the replay is still running
+            self._overlap = self.use_graph and _external_events_work(dev)
             if not self.use_graph:
                 for p in used:
                     p.register_post_accumulate_grad_hook(self._make_hook(bucket_of[p]))
@@ -470,9 +467,6 @@ class DataParallelEngine:
         of PINNED slots: a copy from pageable memory makes the host wait until the stream has drained -- every step would then start
         with an idle GPU waiting for the replay to be enqueued.  A slot is reused only after the copy that read it has finished
         (an event per slot), which also bounds how far the host runs ahead of the GPU (_HYPER_SLOTS steps)."""
-        if os.environ.get("MPHSIR_HYPER_PAGEABLE", "0") == "1":
-            self._hyper.copy_(torch.tensor(values), non_blocking=True)
-            return
         ring = getattr(self, "_hyper_ring", None)
         if ring is None:
             ring = self._hyper_ring = (torch.empty((self._HYPER_SLOTS, len(values)), dtype=torch.float32).pin_memory(), [None] * self._HYPER_SLOTS)

@@ -1,5 +1,6 @@
 """Thin tensor-level wrappers over the C ABI (include/mphsir.h): shape checks, output allocation,
-pointer/stream plumbing.  No arithmetic happens here."""
+pointer/stream plumbing.  No arithmetic happens here.
+The few environment switches read here (measurement and diagnosis only) are documented in the table of tools/README.md."""
 import ctypes
 import os
 import weakref
@@ -154,18 +155,20 @@ class reduce_scope:
 
 
 # The parameter-gradient work of a backward function -- its grouped token-reduction GEMMs and the ordered sums of their partials --
-# feeds nothing but the optimizer.  Inside the engine's backward (deferred_reductions) it can leave the launch stream: DW_SIDE = 1
-# issues the sums, DW_SIDE = 2 the GEMMs and the sums, on a second stream forked at the end of the backward function and joined
+# feeds nothing but the optimizer.  Inside the engine's backward (deferred_reductions) it can leave the launch stream: DW_SIDE = 2
+# (the default; 0 keeps everything on the launch stream) issues the GEMMs and the sums on a second stream forked at the end of the backward function and joined
 # only where gradients are read (end of the backward pass / a bucket hook) -- a parallel branch of the captured graph that fills
 # the CUs the small launches of the lower pyramid levels leave idle, reading the partials while they are still in the Infinity
 # Cache.  Every tensor involved stays referenced until the join (nothing is recycled under the branch).
 DW_SIDE = int(os.environ.get("MPHSIR_DW_SIDE", "2"))
-DW_BATCH_BYTES = int(float(os.environ.get("MPHSIR_DW_BATCH_MB", "256")) * (1 << 20))      # 0 / 24 / 48 / 128 / 256 / 512 MB: 20.90 / 20.82 / 20.75 / 20.67 / 20.60 / 20.63 ms per step (one box, pairs)
+if DW_SIDE not in (0, 2):
+    raise ValueError("mp-hsir_amd: MPHSIR_DW_SIDE must be 0 (sums deferred on the launch stream) or 2 (GEMMs and sums on the weight-gradient branch), got %d" % DW_SIDE)
+DW_BATCH_BYTES = 256 << 20      # 0 / 24 / 48 / 128 / 256 / 512 MB: 20.90 / 20.82 / 20.75 / 20.67 / 20.60 / 20.63 ms per step (one box, pairs)
 _DW = {}      # device -> its _DwBranch
 
 
 class _DwBranch:
-    """the weight-gradient branch of one device: its stream, the batch that waits for its flush (DW_SIDE = 2) and `keep`, every
+    """the weight-gradient branch of one device: its stream, the batch that waits for its flush and `keep`, every
     tensor that work issued on the branch reads or writes (released by the final join)"""
 
     def __init__(self, dev):
@@ -173,11 +176,11 @@ class _DwBranch:
         self.gemms, self.calls, self.segs, self.nbytes, self.keep = [], [], [], 0, []
 
 
-# MPHSIR_DEBUG_DEFERRED=1 (tests): every parameter-gradient sum that is handed out before it has been computed (deferred to the end
+# DEBUG_DEFERRED = True (tests assign it): every parameter-gradient sum that is handed out before it has been computed (deferred to the end
 # of the backward pass, or issued on the weight-gradient branch) is first filled with NaN on the LAUNCH stream -- a consumer that
 # reads or clones it early (a shared parameter, a tensor hook, gradient accumulation into an existing .grad, a strided view that
 # AccumulateGrad has to copy) then yields NaN instead of stale memory, and the engine's finite check after the hand-over trips
-DEBUG_DEFERRED = os.environ.get("MPHSIR_DEBUG_DEFERRED", "0") == "1"
+DEBUG_DEFERRED = False
 
 
 def _hand_out(segs):
@@ -209,22 +212,16 @@ def _dw_side(scope):
     if br is None:
         br = _DW[dev] = _DwBranch(dev)
     _hand_out(scope.segs)
-    if DW_SIDE >= 2:
-        # Small backward functions (the lower pyramid levels: a few MB of operands, launches that cost their 15-30 us floor whatever
-        # they move) are BATCHED: their problems wait until DW_BATCH_BYTES of operands, a full grouped launch (8 problems) or 32 sum
-        # segments have come together, and go out as ONE grouped GEMM launch + ONE ordered-sum launch; a big function flushes at once
-        # (with whatever is pending, in issue order).  The operands stay referenced (the batch, then `keep`).
-        br.gemms += scope.gemms
-        br.calls += scope.calls
-        br.segs += scope.segs
-        br.nbytes += sum(g["M"] * (g["N1"] + g["N2"]) * 2 for g in scope.gemms)
-        if scope.calls or br.nbytes >= DW_BATCH_BYTES or len(br.gemms) + 3 > _lib.TN_GROUP_MAX or len(br.segs) + 17 > _lib.REDUCE_MAX_SEGS:
-            _dw_flush_pending(dev)
-    else:                                   # the GEMMs stay on the launch stream: only their sums fork
-        _flush_calls(scope.calls)
-        _flush_gemms(scope.gemms)
-        br.keep += [g["keep"] for g in scope.gemms + scope.calls]
-        _dw_fork(dev, [], [], scope.segs)
+    # Small backward functions (the lower pyramid levels: a few MB of operands, launches that cost their 15-30 us floor whatever
+    # they move) are BATCHED: their problems wait until DW_BATCH_BYTES of operands, a full grouped launch (8 problems) or 32 sum
+    # segments have come together, and go out as ONE grouped GEMM launch + ONE ordered-sum launch; a big function flushes at once
+    # (with whatever is pending, in issue order).  The operands stay referenced (the batch, then `keep`).
+    br.gemms += scope.gemms
+    br.calls += scope.calls
+    br.segs += scope.segs
+    br.nbytes += sum(g["M"] * (g["N1"] + g["N2"]) * 2 for g in scope.gemms)
+    if scope.calls or br.nbytes >= DW_BATCH_BYTES or len(br.gemms) + 3 > _lib.TN_GROUP_MAX or len(br.segs) + 17 > _lib.REDUCE_MAX_SEGS:
+        _dw_flush_pending(dev)
     return True
 
 
@@ -667,7 +664,7 @@ def _rows(t):
 
 # token GEMM kernel form (include/mphsir.h, mphsir_gemm_args.form): 0 = the library chooses (ring form for input-heavy shapes, K >= 3 N),
 # 1 = one workgroup per token tile, 2 = ring form wherever it applies
-TOK_FORM = int(os.environ.get("MPHSIR_TOK_FORM", "0"))
+TOK_FORM = 0
 
 
 def gemm_tok(x, w, bias=None, ln=None, epi=0, res=None, sa=None, gate=None, keep=None, geom=None, out=None):
@@ -1128,18 +1125,14 @@ def pack_gated_mlp(fc1_w, fc1_b, fc2_w, dtype):
     return W1, b1, W2
 
 
-
-
-BASE_SKIP_FUSED = os.environ.get("MPHSIR_BASE_SKIP_FUSED", "1") == "1"     # BaseBlock's `+ x` inside its last gated-MLP launch (6 launches fewer per forward)
-BASE_SKIP_TRAIN = os.environ.get("MPHSIR_BASE_SKIP_TRAIN", "1") == "1"     # ... in training passes too
-BASE_SKIP_BWD = os.environ.get("MPHSIR_BASE_SKIP_BWD", "1") == "1"         # ... and the skip's gradient added by the first block's last backward launch
-# hidden split of the gated MLP kernels for small launches (< 256 token tiles at C >= 192: the latent level): 0 = off, else the number of
-# workgroups per token tile is chosen so that about 256 workgroups exist
-MLP_HSPLIT = os.environ.get("MPHSIR_MLP_HSPLIT", "1") == "1"
+# BaseBlock's `+ x` runs inside its last gated-MLP launch (6 launches fewer per forward), in training passes too ...
+BASE_SKIP_BWD = True         # ... and the skip's gradient is added by the first block's last backward launch (False: a launch of its own; tests)
 
 
 def mlp_hsplit(M, C, HP):
-    if not MLP_HSPLIT or C < 192 or M // 64 >= 256:
+    """hidden split of the gated MLP kernels for small launches (< 256 token tiles at C >= 192: the latent level): the number of
+    workgroups per token tile, chosen so that about 256 workgroups exist"""
+    if C < 192 or M // 64 >= 256:
         return 1
     s, chunks = 1, HP // 32
     while (M // 64) * s * 2 <= 256 and chunks % (s * 2) == 0:
@@ -1147,8 +1140,8 @@ def mlp_hsplit(M, C, HP):
     return s
 
 
-MLP_FUSE_SUM = os.environ.get("MPHSIR_MLP_FUSE_SUM", "1") == "1"      # the block's branch sum (pass B + gate + residual) inside the gated-MLP launch
-MLP_FUSE_MIN_TILES = int(os.environ.get("MPHSIR_MLP_FUSE_MIN_TILES", "256"))   # ... from this many 128-token tiles (where the plain launch is the eight-wave form too)
+MLP_FUSE_SUM = True      # the block's branch sum (pass B + gate + residual) inside the gated-MLP launch
+MLP_FUSE_MIN_TILES = 256   # ... from this many 128-token tiles (where the plain launch is the eight-wave form too)
 
 
 def gated_mlp_fuses(M, C, HW, dtype):
@@ -1311,10 +1304,6 @@ def dwconv_gram(tq, tk, tv, wq, wk, wv, ldw, B, H, W, C, heads, nsplit=None, kee
     return v, gp, sp, nsplit
 
 
-# training forward through the fused pass A (t and q|k as extra outputs); MPHSIR_FUSED_TRAIN=0 = 1x1 GEMM + depthwise/Gram kernel
-FUSED_TRAIN = os.environ.get("MPHSIR_FUSED_TRAIN", "1") == "1"
-
-
 def qkv_dwconv_gram_fits(C, heads, H, W, dtype):
     return bool(_lib.load().mphsir_qkv_dwconv_gram_fits(C, heads, H, W, _DT[dtype]))
 
@@ -1351,10 +1340,6 @@ def qkv_dwconv_gram_rows_fits(C, heads, H, W, dtype, ln=False):
     return bool(_lib.load().mphsir_qkv_dwconv_gram_rows_fits(C, heads, H, W, _DT[dtype], int(bool(ln))))
 
 
-# the row-walking form: MPHSIR_ROWS_FORM=0 keeps every shape on the tile form
-ROWS_FORM = os.environ.get("MPHSIR_ROWS_FORM", "1") == "1"
-
-
 def choose_row_segments(B, H, W, C, heads):
     """row segments per 32-pixel strip: the most rows per workgroup (least halo recompute: 2 rows per segment) that still
     gives every CU a workgroup"""
@@ -1377,7 +1362,7 @@ def qkv_dwconv_gram(x, wqkv, w9, B, H, W, C, heads, ln=None, nsplit=None, head_g
     assert M == B * H * W and wqkv.shape == (3 * C, C) and wqkv.is_contiguous() and wqkv.dtype == x.dtype
     if row_segments is None:
         row_segments = 0
-        if ROWS_FORM and nsplit is None and head_groups is None and qkv_dwconv_gram_rows_fits(C, heads, H, W, x.dtype, ln is not None):
+        if nsplit is None and head_groups is None and qkv_dwconv_gram_rows_fits(C, heads, H, W, x.dtype, ln is not None):
             row_segments = choose_row_segments(B, H, W, C, heads)
     if row_segments:
         nsplit = (W // 32) * row_segments
@@ -1715,12 +1700,12 @@ def dwconv3x3_bwd(x, dy, w9, col_ranges=None):
 
 
 # ---- backward of the channel attention between the fold and the 1x1 conv in one launch (csrc/spectral_bwd.hip) ----------------
-SPECTRAL_BWD_FUSED = os.environ.get("MPHSIR_SPECTRAL_BWD_FUSED", "1") == "1"     # 0: the three launches it replaces (gemm_tok x2 + dwconv3x3_bwd)
-SPECTRAL_BWD_WGS = int(os.environ.get("MPHSIR_SPECTRAL_BWD_WGS", "512"))          # workgroups per launch aimed at (two per CU)
+SPECTRAL_BWD_WGS = 512          # workgroups per launch aimed at (two per CU)
 
 
 def spectral_dqkv_bwd_fits(C, heads, H, W, dtype):
-    return SPECTRAL_BWD_FUSED and dtype in _HALF and bool(_lib.load().mphsir_spectral_dqkv_bwd_fits(C, heads, H, W, _DT[dtype]))
+    """else the three launches it replaces (gemm_tok x2 + dwconv3x3_bwd)"""
+    return dtype in _HALF and bool(_lib.load().mphsir_spectral_dqkv_bwd_fits(C, heads, H, W, _DT[dtype]))
 
 
 def spectral_dqkv_bwd(qk, d_out, t, W2, MbT, w9, B, H, W, C, heads, nblk=None, round_dall=False):
@@ -1791,26 +1776,25 @@ def gated_mlp_bwd(x, dy, dm, ln_w, ln_b, W1, b1, W1T, W2T, variant=0, keep=None,
     return dx, xn, h, dpre, part
 
 
-MLP_WGRAD = os.environ.get("MPHSIR_MLP_WGRAD", "1") == "1"      # parameter gradients of the gated MLP by recomputation (no h / dpre in HBM)
-MLP_WGRAD_NCH = int(os.environ.get("MPHSIR_MLP_WGRAD_NCH", "0"))  # chunks of 32 hidden units per workgroup: 0 = per shape, 1, 2
-MLP_WGRAD_WGS = int(os.environ.get("MPHSIR_MLP_WGRAD_WGS", "512"))
-MLP_WGRAD_MAXC = int(os.environ.get("MPHSIR_MLP_WGRAD_MAXC", "128"))
-MLP_WGRAD_CAP = float(os.environ.get("MPHSIR_MLP_WGRAD_CAP", "4.0"))   # partial bytes <= this x the bytes of the two token matrices (1 / 2 / 4: 21.04-21.09 / 20.98-20.99 / 20.95-20.97 ms per step: at M = 32768 a full round of workgroups -- 40 ranges instead of 24 -- is worth more than the 9 MB of partials it adds)
+# parameter gradients of the gated MLP by recomputation (no h / dpre in HBM)
+MLP_WGRAD_WGS = 512
+MLP_WGRAD_MAXC = 128
+MLP_WGRAD_CAP = 4.0   # partial bytes <= this x the bytes of the two token matrices (1 / 2 / 4: 21.04-21.09 / 20.98-20.99 / 20.95-20.97 ms per step: at M = 32768 a full round of workgroups -- 40 ranges instead of 24 -- is worth more than the 9 MB of partials it adds)
 
 
 def gated_mlp_wgrad_fits(M, C, HP, dtype):
     """where the library takes the recomputing weight-gradient kernel: 16-bit types, >= 16384 tokens (below, the partials of a range
     outweigh the token matrices), C <= 128 -- at C = 192 the kernel has no registers left for the tile in flight (19 spilled) and
     measured slower than the operand path: remote-sensing fp16 step 27.0 against 26.2 ms, 195-210 against 120 us per launch"""
-    return (MLP_WGRAD and dtype in _HALF and M % 64 == 0 and HP % 32 == 0 and M >= 16384 and C <= MLP_WGRAD_MAXC
+    return (dtype in _HALF and M % 64 == 0 and HP % 32 == 0 and M >= 16384 and C <= MLP_WGRAD_MAXC
             and bool(_lib.load().mphsir_gated_mlp_wgrad_fits(C, 1, _DT[dtype])))
 
 
 def mlp_wgrad_plan(M, C, HP, dtype, nch=None, ranges=None):
-    """(chunks per workgroup, token ranges): ~MLP_WGRAD_WGS workgroups, ranges a multiple of 8, partial bytes capped"""
+    """(chunks of 32 hidden units per workgroup, token ranges): ~MLP_WGRAD_WGS workgroups, ranges a multiple of 8, partial bytes capped"""
     lib = _lib.load()
     if nch is None:
-        nch = MLP_WGRAD_NCH or 1
+        nch = 1
     if not lib.mphsir_gated_mlp_wgrad_fits(C, nch, _DT[dtype]):
         nch = 1
     S = (HP // 32 + nch - 1) // nch
@@ -1883,11 +1867,7 @@ def combine_bwd(dy, sa, gate, keep, shift, want_dsa=True):
     return d_out, d_sa, dgate
 
 
-def win_attn_bwd_fits(C, heads, dtype):
-    return bool(_lib.load().mphsir_win_attn_bwd_fits(C, heads, _DT[dtype]))
-
-
-BRANCH_BWD_FUSED = os.environ.get("MPHSIR_BRANCH_BWD_FUSED", "1") == "1"     # 0: the gemm_tok launch (and combine_bwd's d_sa) it replaces
+BRANCH_BWD_FUSED = True     # False (tests): the gemm_tok launch (and combine_bwd's d_sa) it replaces
 
 
 def win_attn_bwd_dsa_fits(C, heads, dtype):
@@ -1953,13 +1933,9 @@ def ln_bwd_win(x, dxn_w, dres, ln_w, shift):
     return dx, part
 
 
-LN_BWD_DXN = os.environ.get("MPHSIR_LN_BWD_DXN", "1") == "1"      # d_xn = dQKV Wqkv formed inside the LayerNorm-backward launch (0: gemm_tok + ln_bwd_win)
-LN_BWD_DXN_MAX_ROWS = int(os.environ.get("MPHSIR_LN_BWD_DXN_ROWS", "0"))      # 0: every size; else only launches of at most this many token rows
-
-
 def ln_bwd_win_dxn_fits(M, C, dtype):
-    return (LN_BWD_DXN and dtype in _HALF and (LN_BWD_DXN_MAX_ROWS == 0 or M <= LN_BWD_DXN_MAX_ROWS)
-            and bool(_lib.load().mphsir_ln_bwd_win_dxn_fits(C, _DT[dtype])))
+    """d_xn = dQKV Wqkv can be formed inside the LayerNorm-backward launch, at every size (else: gemm_tok + ln_bwd_win)"""
+    return dtype in _HALF and bool(_lib.load().mphsir_ln_bwd_win_dxn_fits(C, _DT[dtype]))
 
 
 def ln_bwd_win_dxn(x, dqkv, wqkvT, dres, ln_w, shift, dres2=None):
@@ -2022,14 +1998,36 @@ def ln_bwd_tok(x2, dxn, dres, ln_w, ln_b):
     return dx, g[0], g[1], xn
 
 
-TN_GROUPED = True          # weight-gradient GEMMs of a backward function in one launch
-TN_BIG_TILES = True        # bf16 token-reduction GEMMs use the transposed-LDS-read kernel (ds_read_b64_tr_b16)
+# Token-reduction GEMMs: the weight-gradient GEMMs of a backward function go out in one grouped launch, and the 16-bit ones use the
+# transposed-LDS-read kernel (ds_read_b64_tr_b16).
 # 16-bit big-tile kernel: 1 = transposed-read kernel (256 threads, ~2 workgroups per CU), 2 = its ring form (512 threads, one per CU),
 # 0 = per problem: the ring form where it measured faster -- ONE output tile, unbatched, >= 65536 tokens (tools/bench/bench_tn.py) -- else 1
-TN_FORM = int(os.environ.get("MPHSIR_TN_FORM", "0"))
+TN_FORM = 0
 TN_RING_WGS = 256          # ring form: workgroups per launch aimed at (one per CU)
-TN_PART_CAP = float(os.environ.get("MPHSIR_TN_PART_CAP", "0.4"))    # 0 / 0.2 / 0.3 / 0.4 / 0.55: 21.59 / 21.82 / 21.47 / 21.43 / 21.45 ms per step (one box)
-TN_BIG_ROUNDS = float(os.environ.get("MPHSIR_TN_ROUNDS", "1.0"))        # ... and aim for this many full rounds of resident workgroups (re-measured with the partial sums deferred: 0.5 / 0.75 / 1 / 2 -> 22.48 / 22.33 / 22.37 / 22.47 ms per step)
+TN_PART_CAP = 0.4    # partial bytes <= this x input bytes (small-M problems: the partials ARE the traffic); 0 / 0.2 / 0.3 / 0.4 / 0.55: 21.59 / 21.82 / 21.47 / 21.43 / 21.45 ms per step (one box)
+TN_BIG_ROUNDS = 1.0        # ... and aim for this many full rounds of resident workgroups (re-measured with the partial sums deferred: 0.5 / 0.75 / 1 / 2 -> 22.48 / 22.33 / 22.37 / 22.47 ms per step)
+
+
+def tn_split(M, N1, N2, dtype, Bt=1, batched=False, tile128=None):
+    """(form, tile128, nsplit) of the token-reduction GEMM (Bt, M, N1)^T (Bt, M, N2): the kernel form, the big-tile kernel or not, and
+    the split of the token axis gemm_tn takes when the caller names none"""
+    half = dtype in _HALF
+    if tile128 is None:
+        tile128 = half
+    form = TN_FORM or (2 if (N1 <= 128 and N2 <= 128 and not batched and M >= 65536) else 1)
+    if tile128 and half:     # transposed-read kernel: 64/128-wide tile per operand, 2 workgroups per CU
+        tiles = ((N1 + 127) // 128 if N1 > 64 else 1) * ((N2 + 127) // 128 if N2 > 64 else 1) * Bt
+        if form == 2:                    # ring form: one 512-thread workgroup per CU
+            nsplit = max(1, min(M // 256, 128, max(1, TN_RING_WGS // tiles)))
+        else:
+            resident = 2 if (N1 > 64 and N2 > 64) else (4 if (N1 <= 64 and N2 <= 64) else 3)    # workgroups per CU (LDS, VGPRs)
+            nsplit = max(1, min(M // 256, 128, max(1, int(256 * resident * TN_BIG_ROUNDS) // tiles)))
+    else:
+        ts = 128 if tile128 else 64
+        tiles = ((N1 + ts - 1) // ts) * ((N2 + ts - 1) // ts) * Bt
+        nsplit = max(1, min(M // 512, 64, max(1, 768 // tiles)))      # ~3 workgroups per CU (measured optimum)
+    cap = int(TN_PART_CAP * M * (N1 + N2) * (2 if half else 4) / (N1 * N2 * 4.0))
+    return form, tile128, max(1, (M + 4095) // 4096, min(nsplit, cap))
 
 
 def gemm_tn(a, b, nsplit=None, colsum=False, tile128=None, immediate=False, reduce=True):
@@ -2042,27 +2040,12 @@ def gemm_tn(a, b, nsplit=None, colsum=False, tile128=None, immediate=False, redu
     Bt = a.shape[0] if batched else 1
     M, N1, N2 = a.shape[-2], a.shape[-1], b.shape[-1]
     assert a.stride(-1) == 1 and b.stride(-1) == 1 and b.shape[-2] == M and a.dtype == b.dtype
-    if tile128 is None:
-        tile128 = TN_BIG_TILES and a.dtype in _HALF
-    form = TN_FORM or (2 if (N1 <= 128 and N2 <= 128 and not batched and M >= 65536) else 1)
+    form, tile128, split = tn_split(M, N1, N2, a.dtype, Bt, batched, tile128)
     if nsplit is None:
-        if tile128 and a.dtype in _HALF:     # transposed-read kernel: 64/128-wide tile per operand, 2 workgroups per CU
-            tiles = ((N1 + 127) // 128 if N1 > 64 else 1) * ((N2 + 127) // 128 if N2 > 64 else 1) * Bt
-            if form == 2:                    # ring form: one 512-thread workgroup per CU
-                nsplit = max(1, min(M // 256, 128, max(1, TN_RING_WGS // tiles)))
-            else:
-                resident = 2 if (N1 > 64 and N2 > 64) else (4 if (N1 <= 64 and N2 <= 64) else 3)    # workgroups per CU (LDS, VGPRs)
-                nsplit = max(1, min(M // 256, 128, max(1, int(256 * resident * TN_BIG_ROUNDS) // tiles)))
-        else:
-            ts = 128 if tile128 else 64
-            tiles = ((N1 + ts - 1) // ts) * ((N2 + ts - 1) // ts) * Bt
-            nsplit = max(1, min(M // 512, 64, max(1, 768 // tiles)))      # ~3 workgroups per CU (measured optimum)
-        if TN_PART_CAP > 0:                      # partial bytes <= TN_PART_CAP x input bytes (small-M problems: the partials ARE the traffic)
-            cap = int(TN_PART_CAP * M * (N1 + N2) * a.element_size() / (N1 * N2 * 4.0))
-            nsplit = max(1, (M + 4095) // 4096, min(nsplit, cap))
+        nsplit = split
     part = torch.empty((Bt, nsplit, N1, N2), dtype=torch.float32, device=a.device)
     cs = torch.empty((Bt, nsplit, N1), dtype=torch.float32, device=a.device) if colsum else None
-    if _SCOPE is not None and TN_GROUPED and not immediate and not batched and tile128 and a.dtype in _HALF:
+    if _SCOPE is not None and not immediate and not batched and tile128 and a.dtype in _HALF:
         # nothing but the partial reduction at the end of the scope reads the result: issue it there, grouped
         _SCOPE.gemms.append(dict(A=a.data_ptr(), lda=a.stride(-2), B=b.data_ptr(), ldb=b.stride(-2), Cpart=part.data_ptr(),
                                  cs=cs.data_ptr() if colsum else None, M=M, N1=N1, N2=N2, nsplit=nsplit, form=form,
@@ -2133,7 +2116,7 @@ def dwconv_gate_bwd(t, w9, du, B, H, W):
     return u, dt_
 
 
-FOLD_BWD_DM_MAX_TOKENS = int(os.environ.get("MPHSIR_FOLD_BWD_DM_TOKENS", "1024"))      # per sample; 0: always the token-reduction GEMM
+FOLD_BWD_DM_MAX_TOKENS = 1024      # per sample; above: the token-reduction GEMM
 
 
 def fold_bwd_forms_dm(N, C, heads, dtype):
@@ -2265,6 +2248,12 @@ def conv3x3_tok(x, wp, out=None):
     return y
 
 
+def conv3x3_wgrad_split(M, Np, Cp):
+    """the token-axis split conv3x3_wgrad takes when the caller names none: one round of resident workgroups over the output tiles"""
+    tiles = ((Np + 127) // 128 if Np > 64 else 1) * ((9 * Cp + 127) // 128)
+    return max(1, min(M // 256, 128, max(1, (TN_RING_WGS if TN_FORM == 2 else int(256 * 2 * TN_BIG_ROUNDS)) // tiles)))
+
+
 def conv3x3_wgrad(dy2, x, nsplit=None, cout=None, cin=None):
     """dy2 (M, Np) [Np % 8 == 0], x (B,H,W,Cp) contiguous [Cp % 8 == 0], 16-bit: the weight gradient of a dense 3x3 conv with the
     im2col gather inside the token-reduction GEMM.  -> fp32 (Np, 9*Cp) in (tap, channel) column order; with cout / cin given:
@@ -2276,8 +2265,7 @@ def conv3x3_wgrad(dy2, x, nsplit=None, cout=None, cin=None):
     M, Np = dy2.shape
     assert x.is_contiguous() and dy2.stride(1) == 1 and M == B * H * W and x.dtype == dy2.dtype and x.dtype in _HALF
     if nsplit is None:
-        tiles = ((Np + 127) // 128 if Np > 64 else 1) * ((9 * Cp + 127) // 128)
-        nsplit = max(1, min(M // 256, 128, max(1, (TN_RING_WGS if TN_FORM == 2 else int(256 * 2 * TN_BIG_ROUNDS)) // tiles)))
+        nsplit = conv3x3_wgrad_split(M, Np, Cp)
     part = torch.empty((1, nsplit, Np, 9 * Cp), dtype=torch.float32, device=x.device)
     _lib.check(lib.mphsir_conv3x3_wgrad(_p(dy2), dy2.stride(0), _p(x), Cp, _p(part), B, H, W, Np, Cp, nsplit, TN_FORM or 1, _DT[x.dtype],
                                         _stream(x)), "conv3x3_wgrad")

@@ -1,5 +1,5 @@
-"""Checks of the window-attention backward that forms the total d_sa itself (ops.win_attn_bwd branch=..., switch
-MPHSIR_BRANCH_BWD_FUSED), shared by the CPU-emulator tests (tests/test_branch_bwd_emu.py) and the MI355X tests
+"""Checks of the window-attention backward that forms the total d_sa itself (ops.win_attn_bwd branch=..., attribute
+ops.BRANCH_BWD_FUSED), shared by the CPU-emulator tests (tests/test_branch_bwd_emu.py) and the MI355X tests
 (tests/test_branch_bwd_gpu.py).  Each kernel check is one tiny launch; the whole-block runs are computed once per
 (case, shift, switch) and shared by the accuracy and the determinism tests."""
 import torch
@@ -16,7 +16,7 @@ GUARDED = ("dx", "norm1.", "attn.qkv.", "attn.proj.", "local_spectral_attn.")
 
 
 class branch_bwd_fused:
-    """`with branch_bwd_fused(on):` runs the attention backward with the switch MPHSIR_BRANCH_BWD_FUSED at `on`.  The capability
+    """`with branch_bwd_fused(on):` runs the attention backward with the attribute ops.BRANCH_BWD_FUSED at `on`.  The capability
     predicate (ops.win_attn_bwd_dsa_fits) is the production one; the tuning rule (ops.win_attn_bwd_dsa_pays: only where one workgroup
     owns a window, i.e. from 512 windows on) is told to take the path at the 8 windows of the whole-block shape too."""
 

@@ -1,4 +1,4 @@
-"""The window-attention backward that forms the total d_sa itself (MPHSIR_BRANCH_BWD_FUSED), on the CPU emulator: the same
+"""The window-attention backward that forms the total d_sa itself (ops.BRANCH_BWD_FUSED), on the CPU emulator: the same
 checks as tests/test_branch_bwd_gpu.py (tests/branch_bwd_checks.py), device = cpu."""
 import pytest
 import torch

@@ -648,10 +648,10 @@ def test_no_parameter_gradient_is_read_before_its_sum(model, dw_side, monkeypatc
     assert torch.equal(grads[0], grads[1])
 
 
-@pytest.mark.parametrize("dw_side", [0, 1, 2])
+@pytest.mark.parametrize("dw_side", [0, 2])
 def test_deferred_parameter_gradient_sums_are_bitwise_the_immediate_ones(dw_side, monkeypatch):
     """The engine collects the partial-sum reductions of all parameter gradients of a backward pass and launches them together
-    (ops.deferred_reductions; dw_side = 0) or issues them -- with (2) or without (1) the weight-gradient GEMMs -- on a second
+    (ops.deferred_reductions; dw_side = 0) or issues them -- with the weight-gradient GEMMs (2) -- on a second
     stream beside the data-gradient chain.  Every gradient must be bitwise what the per-function launches produce -- in particular
     no gradient may be read (cloned by AccumulateGrad) before its sum has been launched, and nothing may be recycled under the
     side branch."""

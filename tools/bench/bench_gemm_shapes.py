@@ -1,5 +1,7 @@
 """Diagnostic: which gemm_tok / gemm_tn shapes does one training step launch, and how fast is each?
-Records every call of one eager step of the bench workload, then times each distinct shape in isolation."""
+Records every call of one eager step of the bench workload, then times each distinct shape in isolation.
+    python tools/bench/bench_gemm_shapes.py [batch] [--form 0|1|2]     (--form pins the token-GEMM kernel form: ops.TOK_FORM)"""
+import argparse
 import collections
 import sys
 import os
@@ -11,7 +13,12 @@ from mp_hsir_amd.engine import DataParallelEngine
 from mp_hsir_amd.net.MP_HSIR import MP_HSIR_Net
 
 dev = torch.device("cuda")
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
+ap = argparse.ArgumentParser()
+ap.add_argument("batch", nargs="?", type=int, default=32)
+ap.add_argument("--form", type=int, default=0, choices=(0, 1, 2))
+args = ap.parse_args()
+B = args.batch
+ops.TOK_FORM = args.form
 net = MP_HSIR_Net(compute_dtype=torch.bfloat16, clip_prompt="surrogate").to(dev).train()
 eng = DataParallelEngine(net, lr=2e-4)
 src = SyntheticPatchSource(31, 64, B, 6, dev, 2024, 0)

@@ -20,7 +20,7 @@ sweep)
 side)
   for X in "" "--forward-only --patch 512 --batch 1" "--forward-only --batch 16"; do
     echo "### $X"
-    for e in "X=1" "MPHSIR_SIDE_BRANCH=0" "MPHSIR_DW_SIDE=0" "MPHSIR_DW_SIDE=1" "MPHSIR_PROMPT_SIDE=0" "MPHSIR_SIDE_BRANCH=0 MPHSIR_DW_SIDE=0" \
+    for e in "X=1" "MPHSIR_SIDE_BRANCH=0" "MPHSIR_DW_SIDE=0" "MPHSIR_PROMPT_SIDE=0" "MPHSIR_SIDE_BRANCH=0 MPHSIR_DW_SIDE=0" \
              "MPHSIR_SIDE_BRANCH=0 MPHSIR_DW_SIDE=0 MPHSIR_PROMPT_SIDE=0" "X=1"; do
       echo "$e: $(line $e)"
     done
