@@ -904,9 +904,8 @@ int mphsir_scaler_update(float* scaler, float growth_factor, float backoff_facto
  *   ema untouched.  The arithmetic on p / m / v keeps the order of mphsir_flat_adamw: with stats == NULL or stats[1] == 1, and
  *   ema == NULL, the result is BITWISE that of mphsir_flat_adamw (with a scaler: of mphsir_flat_adamw_scaled).
  * Both refuse (MPHSIR_EINVAL, nothing launched): another struct_size, a null or misaligned arena, n <= 0 or n % 4 != 0, a workspace
- *   that is too small or not 8-byte aligned, max_norm <= 0 or NaN, ema_decay outside [0, 1), null stats in mphsir_grad_norm.
- * (Declared as `struct ...; typedef ...;` because these are the first args structs with float members.)                          */
-struct mphsir_grad_norm_args {
+ *   that is too small or not 8-byte aligned, max_norm <= 0 or NaN, ema_decay outside [0, 1), null stats in mphsir_grad_norm.   */
+typedef struct mphsir_grad_norm_args {
     uint32_t struct_size;       /* = sizeof(this struct), set by the caller: any other value is rejected with MPHSIR_EINVAL */
     const float* g;
     int64_t n;
@@ -916,11 +915,10 @@ struct mphsir_grad_norm_args {
     void* workspace;
     int64_t workspace_bytes;
     float* stats;
-};
-typedef struct mphsir_grad_norm_args mphsir_grad_norm_args;
+} mphsir_grad_norm_args;
 int64_t mphsir_grad_norm_workspace_bytes(int64_t n);
 int mphsir_grad_norm(const mphsir_grad_norm_args* a, void* stream);
-struct mphsir_flat_adamw_ex_args {
+typedef struct mphsir_flat_adamw_ex_args {
     uint32_t struct_size;       /* = sizeof(this struct), set by the caller: any other value is rejected with MPHSIR_EINVAL */
     float* p;
     const float* g;
@@ -934,8 +932,7 @@ struct mphsir_flat_adamw_ex_args {
     const float* hyper;
     const float* scaler;
     const float* stats;
-};
-typedef struct mphsir_flat_adamw_ex_args mphsir_flat_adamw_ex_args;
+} mphsir_flat_adamw_ex_args;
 int mphsir_flat_adamw_ex(const mphsir_flat_adamw_ex_args* a, void* stream);
 
 /* ---- flat-arena utilities -------------------------------------------------------------------------
@@ -1000,9 +997,9 @@ int mphsir_l1_clamp_loss(const float* y, const float* clean, float* grad, float*
  * workspace: mphsir_spectral_loss_workspace_bytes(B, C, H, W) bytes, 8-byte aligned, caller-owned (negative: sizes refused).
  * Refused (MPHSIR_EINVAL, nothing launched): another struct_size; a null y / clean / out / workspace; B, C, H or W < 1 or more than
  * 2^31 - 1 workgroups; a weight that is negative or not finite; both weights 0 (that loss is mphsir_l1_clamp_loss); a workspace that is
- * too small or not 8-byte aligned.  (Declared as `struct ...; typedef ...;` like the optimizer structs: it has float members.)      */
+ * too small or not 8-byte aligned.   */
 #define MPHSIR_SAM_MIN_SIN 1e-6
-struct mphsir_spectral_loss_args {
+typedef struct mphsir_spectral_loss_args {
     uint32_t struct_size;       /* = sizeof(this struct), set by the caller: any other value is rejected with MPHSIR_EINVAL */
     const float* y;
     const float* clean;
@@ -1012,8 +1009,7 @@ struct mphsir_spectral_loss_args {
     int64_t workspace_bytes;
     int32_t B, C, H, W;
     float w_sam, w_sdiff;
-};
-typedef struct mphsir_spectral_loss_args mphsir_spectral_loss_args;
+} mphsir_spectral_loss_args;
 int64_t mphsir_spectral_loss_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
 int mphsir_spectral_loss(const mphsir_spectral_loss_args* a, void* stream);
 
@@ -1043,7 +1039,7 @@ int mphsir_spectral_loss(const mphsir_spectral_loss_args* a, void* stream);
  * Refused (MPHSIR_EINVAL, nothing launched): another struct_size; a null y / clean / out / workspace; H < 7 or W < 7; B or C < 1, H W >=
  * 2^31 or more than 2^31 - 1 workgroups; a weight that is not finite or <= 0; accumulate other than 0 / 1, or 1 without grad; a workspace
  * that is too small or not 8-byte aligned.                                                                                          */
-struct mphsir_ssim_loss_args {
+typedef struct mphsir_ssim_loss_args {
     uint32_t struct_size;       /* = sizeof(this struct), set by the caller: any other value is rejected with MPHSIR_EINVAL */
     const float* y;
     const float* clean;
@@ -1055,8 +1051,7 @@ struct mphsir_ssim_loss_args {
     int32_t B, C, H, W;
     float w_ssim;
     int32_t accumulate;
-};
-typedef struct mphsir_ssim_loss_args mphsir_ssim_loss_args;
+} mphsir_ssim_loss_args;
 int64_t mphsir_ssim_loss_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
 int mphsir_ssim_loss(const mphsir_ssim_loss_args* a, void* stream);
 

@@ -9,7 +9,8 @@ import torch
 
 from . import _lib
 
-_DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}     # dtype codes of include/mphsir.h
+_K = _lib.CONSTANTS                                                # the #defines of include/mphsir.h
+_DT = {torch.float32: _K["MPHSIR_F32"], torch.bfloat16: _K["MPHSIR_BF16"], torch.float16: _K["MPHSIR_F16"]}     # dtype codes
 _HALF = (torch.bfloat16, torch.float16)                            # 16-bit storage, fp32 accumulation
 
 # optional algorithmic work accounting (bench.py roofline leg): kernel name -> [launches, flops, bytes]
@@ -317,7 +318,7 @@ def _flush_gemms(gemms):
         # one launch = one element type on one device (a batch of the weight-gradient branch can mix backward functions: ADVICE r05)
         k0 = chunk[0]["keep"][0]
         assert all(g["keep"][0].dtype == k0.dtype and g["keep"][0].device == k0.device for g in chunk), "grouped token-reduction GEMMs of mixed dtype / device"
-        arr = (_lib.TnProblem * len(chunk))()
+        arr = (_lib.GemmTnProblem * len(chunk))()
         for k, g in enumerate(chunk):
             q = arr[k]
             q.A, q.lda, q.B, q.ldb, q.Cpart, q.colsum_part = g["A"], g["lda"], g["B"], g["ldb"], g["Cpart"], g["cs"]
@@ -516,19 +517,22 @@ def _workspace_bytes(op, refusal, *sizes):
     return nbytes
 
 
-_SPECTRAL_WS = {}      # (device, stream, bytes) -> the float64 block partials of mphsir_spectral_loss, reused from call to call
+_LOSS_WS = {}      # (op, device, stream, bytes) -> the float64 block partials of a loss launch pair, reused from call to call
+
+
+def _loss_workspace(op, refusal, y):
+    """the workspace mphsir_<op> needs for a (B,C,H,W) cube like y, one per (op, device, stream, size): launch 2 has consumed it when the
+    call returns to the stream, so the next call on that stream may overwrite it"""
+    nbytes = _workspace_bytes(op, refusal, *y.shape)
+    key = (op, y.device, torch.cuda.current_stream(y.device).cuda_stream if y.is_cuda else 0, nbytes)
+    ws = _LOSS_WS.get(key)
+    if ws is None:
+        ws = _LOSS_WS[key] = torch.empty((nbytes // 8,), dtype=torch.float64, device=y.device)
+    return ws
 
 
 def spectral_loss_workspace(y):
-    """the workspace mphsir_spectral_loss needs for a (B,C,H,W) cube like y, one per (device, stream, size): launch 2 has consumed it
-    when the call returns to the stream, so the next call on that stream may overwrite it"""
-    B, C, H, W = y.shape
-    nbytes = _workspace_bytes("spectral_loss", "spectral_loss refuses (B %d, C %d, H %d, W %d)", B, C, H, W)
-    key = (y.device, torch.cuda.current_stream(y.device).cuda_stream if y.is_cuda else 0, nbytes)
-    ws = _SPECTRAL_WS.get(key)
-    if ws is None:
-        ws = _SPECTRAL_WS[key] = torch.empty((nbytes // 8,), dtype=torch.float64, device=y.device)
-    return ws
+    return _loss_workspace("spectral_loss", "spectral_loss refuses (B %d, C %d, H %d, W %d)", y)
 
 
 def _spectral_loss_launch(y, clean, w_sam, w_sdiff, want_grad):
@@ -583,19 +587,8 @@ def spectral_loss_grad(y, clean, w_sam, w_sdiff):
     return out[0], g, out
 
 
-_SSIM_WS = {}          # (device, stream, bytes) -> the float64 block partials of mphsir_ssim_loss, reused from call to call
-
-
 def ssim_loss_workspace(y):
-    """the workspace mphsir_ssim_loss needs for a (B,C,H,W) cube like y, one per (device, stream, size): launch 2 has consumed it when
-    the call returns to the stream, so the next call on that stream may overwrite it"""
-    B, C, H, W = y.shape
-    nbytes = _workspace_bytes("ssim_loss", "ssim_loss refuses (B %d, C %d, H %d, W %d: H, W >= 7)", B, C, H, W)
-    key = (y.device, torch.cuda.current_stream(y.device).cuda_stream if y.is_cuda else 0, nbytes)
-    ws = _SSIM_WS.get(key)
-    if ws is None:
-        ws = _SSIM_WS[key] = torch.empty((nbytes // 8,), dtype=torch.float64, device=y.device)
-    return ws
+    return _loss_workspace("ssim_loss", "ssim_loss refuses (B %d, C %d, H %d, W %d: H, W >= 7)", y)
 
 
 def _ssim_loss_launch(y, clean, w_ssim, base_loss, grad, want_grad):
@@ -960,9 +953,10 @@ def quality_meter(table, row, psnr, ssim, sam_deg, sam_pixels, use=None, n=None,
     return table
 
 
-DEG_KINDS = {"none": 0, "gaussianN": 1, "complexN": 2, "blur": 3, "motion_blur": 3, "circle_blur": 3, "sr": 4, "inpaint": 5, "bandmiss": 6,
-             "haze": 7, "cassi": 0} # MPHSIR_DEG_* of include/mphsir.h (every blur is a stencil); poissonN has no fused form; cassi is `none`
-                                    # in that launch: its samples are overwritten by the launch pair of ops.cassi
+DEG_KINDS = {name: _K["MPHSIR_DEG_" + kind] for name, kind in (
+    ("none", "NONE"), ("gaussianN", "GAUSSIAN"), ("complexN", "COMPLEX"), ("blur", "BLUR"), ("motion_blur", "BLUR"), ("circle_blur", "BLUR"),
+    ("sr", "SR"), ("inpaint", "INPAINT"), ("bandmiss", "BANDMISS"), ("haze", "HAZE"), ("cassi", "NONE"))}
+# every blur is a stencil; poissonN has no fused form; cassi is `none` in that launch: its samples are overwritten by the launch pair of ops.cassi
 _DEG_TABLES = (("task", torch.int32, "b"), ("aug", torch.int32, "b"), ("param", torch.float32, "b"), ("sub", torch.int32, "b"),
                ("band_sigma", torch.float32, "bc"), ("band_flag", torch.uint8, "bc"), ("col_dead", torch.uint8, "bcn"),
                ("col_off", torch.float32, "bcn"), ("stencils", torch.float32, "k"), ("cirrus", torch.float32, "bnn"),

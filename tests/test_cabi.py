@@ -20,13 +20,15 @@ def lib():
 
 
 def declared_symbols():
+    """every `mphsir_name (` outside a comment: deliberately not the parser of mp_hsir_amd._lib, so that a prototype it skips is caught"""
     text = open(os.path.join(ROOT, "include", "mphsir.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(mphsir_[a-z0-9_]+)\s*\(", text)))
+    return sorted(set(re.findall(r"\b(mphsir_\w+)\s*\(", text)))
 
 
 def test_every_declared_symbol_is_exported(lib):
-    names = declared_symbols()
+    import mp_hsir_amd._lib as L
+    names = L.symbols()
     assert len(names) >= 10
     for n in names:
         assert hasattr(lib, n), "libmphsir.so does not export %s" % n
@@ -34,7 +36,7 @@ def test_every_declared_symbol_is_exported(lib):
 
 def test_python_binding_covers_the_header():
     import mp_hsir_amd._lib as L
-    assert sorted(L.symbols()) == declared_symbols()
+    assert L.symbols() == declared_symbols() and len(L.symbols()) == 92
 
 
 def test_version_and_error_text(lib):
@@ -83,62 +85,49 @@ def test_workspace_size_queries_match_the_python_allocations(lib):
     assert lib.mphsir_gemm_tn_workspace_bytes(0, 1, 1, 1, 0) < 0
 
 
-# ---- the three descriptions of every args struct agree: include/mphsir.h, the ctypes mirror, INTEGRATION.md ------------------------
-_CTYPE_OF = {"uint32_t": ctypes.c_uint32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "int": ctypes.c_int}
-
-
-def header_structs():
-    """{struct name: [(field, ctypes type)]} of every `typedef struct mphsir_* {...}` in include/mphsir.h, in declaration order"""
-    text = open(os.path.join(ROOT, "include", "mphsir.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    out = {}
-    for name, body in re.findall(r"typedef struct (mphsir_\w+) \{(.*?)\}\s*\1;", text, flags=re.S):
-        fields = []
-        for decl in body.split(";"):
-            decl = " ".join(decl.split())
-            if not decl:
-                continue
-            if "*" in decl:                                     # one or more pointers of one type: `const float* a` (one per declaration)
-                m = re.match(r"^(?:const )?\w+\s*\*\s*(\w+)$", decl)
-                assert m, "cannot parse %r in %s" % (decl, name)
-                fields.append((m.group(1), ctypes.c_void_p))
-            else:
-                ty, names = decl.split(" ", 1)
-                for n in names.split(","):
-                    fields.append((n.strip(), _CTYPE_OF[ty]))
-        out[name] = fields
-    return out
-
-
-def test_header_structs_match_the_ctypes_mirrors():
+# ---- the args structs: mp_hsir_amd._lib builds them from include/mphsir.h, so what is pinned here is the header itself --------------------
+def test_every_args_struct_starts_with_its_size():
     import mp_hsir_amd._lib as L
-    hs = header_structs()
-    mirrors = {c.__doc__.split("struct ")[1].split()[0]: c for c in vars(L).values()
-               if isinstance(c, type) and issubclass(c, ctypes.Structure) and c.__doc__ and "mirror of struct" in c.__doc__}
-    assert sorted(mirrors) == sorted(hs), "a struct of the header has no ctypes mirror (or the other way round)"
-    assert sum(n.endswith("_args") for n in hs) >= 14
-    for name, fields in hs.items():
-        got = [(n, t) for n, t in mirrors[name]._fields_]
-        want = [(n, t) for n, t in fields]
-        assert [n for n, _ in got] == [n for n, _ in want], "%s: field names / order differ: %s vs %s" % (name, got, want)
-        for (n, tg), (_, tw) in zip(got, want):
-            assert ctypes.sizeof(tg) == ctypes.sizeof(tw), "%s.%s: %s vs %s" % (name, n, tg, tw)
-        if name.endswith("_args"):
-            assert fields[0] == ("struct_size", ctypes.c_uint32), "%s must start with struct_size" % name
-            assert mirrors[name]().struct_size == ctypes.sizeof(mirrors[name])
+    args = {n: c for n, c in L.STRUCTS.items() if n.endswith("_args")}
+    assert len(L.STRUCTS) == 30 and len(args) == 28 and sorted(set(L.STRUCTS) - set(args)) == ["mphsir_gemm_tn_problem", "mphsir_reduce_seg"]
+    for name, cls in L.STRUCTS.items():
+        assert getattr(L, cls.__name__) is cls and issubclass(cls, L._Args) == (name in args), name
+    for name, cls in args.items():
+        assert cls._fields_[0] == ("struct_size", ctypes.c_uint32), "%s must start with struct_size" % name
+        assert cls().struct_size == ctypes.sizeof(cls)
+
+
+def test_the_float_bearing_args_structs_are_frozen():
+    """the ABI freeze of the optimizer and loss structs: member lists, float members, entry points, their place in INTEGRATION.md"""
+    import mp_hsir_amd._lib as L
+
+    def members(cls, ty=None):
+        return [n for n, t in cls._fields_[1:] if ty is None or t is ty]
+
+    assert members(L.SpectralLossArgs) == ["y", "clean", "grad", "out", "workspace", "workspace_bytes", "B", "C", "H", "W", "w_sam", "w_sdiff"]
+    assert members(L.SsimLossArgs) == ["y", "clean", "grad", "base_loss", "out", "workspace", "workspace_bytes", "B", "C", "H", "W", "w_ssim", "accumulate"]
+    assert members(L.SpectralLossArgs, ctypes.c_float) == ["w_sam", "w_sdiff"] and members(L.SsimLossArgs, ctypes.c_float) == ["w_ssim"]
+    assert members(L.GradNormArgs, ctypes.c_float) == ["grad_scale", "max_norm"]
+    assert members(L.FlatAdamwExArgs, ctypes.c_float) == ["lr", "beta1", "beta2", "eps", "weight_decay", "grad_scale", "ema_decay"]
+    assert {"mphsir_grad_norm", "mphsir_grad_norm_workspace_bytes", "mphsir_flat_adamw_ex", "mphsir_spectral_loss", "mphsir_spectral_loss_workspace_bytes",
+            "mphsir_ssim_loss", "mphsir_ssim_loss_workspace_bytes"} <= set(L.symbols())
+    md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for name in ("mphsir_grad_norm_args", "mphsir_flat_adamw_ex_args", "mphsir_spectral_loss_args", "mphsir_ssim_loss_args"):
+        assert name in md, name
+    assert L.CONSTANTS["MPHSIR_K_COUNT"] == 41, "the SSIM pair launches under the ids of the spectral-loss pair"
 
 
 def test_integration_md_structs_match_the_header():
     """The binding INTEGRATION.md shows a maintainer is executable ctypes code: its Structure classes must be the header's structs
     (round 5 shipped a doc whose MlpArgs ended 13 fields early)."""
+    import mp_hsir_amd._lib as L
     md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    hs = header_structs()
     found = 0
     for cls, comment, body in re.findall(r"class (\w+)\(ctypes\.Structure\):\s*#\s*struct (mphsir_\w+)[^\n]*\n(\s+_fields_ = \[.*?\])[ \t]*(?:#[^\n]*)?\n", md, flags=re.S):
         ns = {"ctypes": ctypes}
         exec("class %s(ctypes.Structure):\n%s" % (cls, body), ns)
         got = ns[cls]._fields_
-        want = hs[comment]
+        want = L.STRUCTS[comment]._fields_
         assert [n for n, _ in got] == [n for n, _ in want], "INTEGRATION.md %s != %s" % (cls, comment)
         assert all(ctypes.sizeof(a[1]) == ctypes.sizeof(b[1]) for a, b in zip(got, want))
         found += 1
@@ -157,3 +146,73 @@ def test_a_short_args_struct_is_refused(lib):
     g = L.GemmArgs()
     g.struct_size = 0
     assert lib.mphsir_gemm_tok(ctypes.byref(g), 1, None) == -1 and b"struct_size" in lib.mphsir_last_error()
+
+
+# ---- the header parser of mp_hsir_amd._lib on synthetic headers (no library) -------------------------------------------------------------
+GOOD_HEADER = """
+#define MPHSIR_EBAD (-3)   /* a comment */
+#define MPHSIR_TINY 1e-6
+#define MPHSIR_MASK 0x10
+typedef struct mphsir_toy_args {
+    uint32_t struct_size;   /* = sizeof */
+    const float* w9; float scale, bias;
+    int64_t n; int32_t B, H;
+} mphsir_toy_args;
+typedef struct mphsir_toy_seg { const void* src; int32_t n; } mphsir_toy_seg;
+const char* mphsir_toy_name(int kid);
+int mphsir_toy(const mphsir_toy_args* a, int dtype, void* stream);
+int64_t mphsir_toy_bytes(int32_t B, int32_t form /* 1 | 2 */,
+                         int32_t* KL, const mphsir_toy_seg* segs,
+                         float scale);
+int mphsir_toy_none(void);
+"""
+
+
+def test_parser_accepts_the_constructs_of_the_header():
+    import mp_hsir_amd._lib as L
+    structs, protos, consts = L.parse_header(GOOD_HEADER)
+    assert consts == {"MPHSIR_EBAD": -3, "MPHSIR_TINY": 1e-6, "MPHSIR_MASK": 16} and isinstance(consts["MPHSIR_TINY"], float)
+    toy, seg = structs["mphsir_toy_args"], structs["mphsir_toy_seg"]
+    assert list(structs) == ["mphsir_toy_args", "mphsir_toy_seg"] and (toy.__name__, seg.__name__) == ("ToyArgs", "ToySeg")
+    assert toy._fields_ == [("struct_size", ctypes.c_uint32), ("w9", ctypes.c_void_p), ("scale", ctypes.c_float), ("bias", ctypes.c_float),
+                            ("n", ctypes.c_int64), ("B", ctypes.c_int32), ("H", ctypes.c_int32)]
+    assert issubclass(toy, L._Args) and toy(n=3).struct_size == ctypes.sizeof(toy) == 40
+    assert not issubclass(seg, L._Args) and seg._fields_ == [("src", ctypes.c_void_p), ("n", ctypes.c_int32)]
+    assert protos == {"mphsir_toy_name": (ctypes.c_char_p, [ctypes.c_int]),
+                      "mphsir_toy": (ctypes.c_int, [ctypes.POINTER(toy), ctypes.c_int, ctypes.c_void_p]),
+                      "mphsir_toy_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(seg), ctypes.c_float]),
+                      "mphsir_toy_none": (ctypes.c_int, [])}
+
+
+@pytest.mark.parametrize("name,text", [
+    ("mphsir_a_args", "typedef struct mphsir_a_args { uint32_t struct_size; float taps[9]; } mphsir_a_args;"),                          # array member
+    ("mphsir_b_args", "typedef struct mphsir_b_args { uint32_t struct_size; struct { int32_t x; } in; } mphsir_b_args;"),              # nested struct
+    ("mphsir_c_args", "typedef struct mphsir_c_args { uint32_t struct_size; union { int32_t i; float f; } u; } mphsir_c_args;"),       # nested union
+    ("mphsir_d_args", "typedef struct mphsir_d_args { uint32_t struct_size; int (*done)(int); } mphsir_d_args;"),                      # function pointer member
+    ("mphsir_e_args", "typedef struct mphsir_e_args { uint32_t struct_size; int32_t on : 1; } mphsir_e_args;"),                        # bit-field
+    ("mphsir_f_args", "typedef struct mphsir_f_args { uint32_t struct_size; size_t n; } mphsir_f_args;"),                              # unknown type name
+    ("mphsir_g_args", "typedef struct mphsir_g_args { uint32_t struct_size; float** rows; } mphsir_g_args;"),                          # pointer to pointer
+    ("mphsir_h_args", "struct mphsir_h_args { uint32_t struct_size; };"),                                                              # a struct without its typedef
+    ("mphsir_fn_a", "int mphsir_fn_a(int (*done)(int), void* stream);"),                                                               # function pointer argument
+    ("mphsir_fn_b", "int mphsir_fn_b(unsigned n, void* stream);"),                                                                     # unknown type name
+    ("mphsir_fn_c", "int mphsir_fn_c(float** rows, void* stream);"),                                                                   # pointer to pointer
+    ("mphsir_fn_d", "int mphsir_fn_d(const mphsir_nowhere_args* a, void* stream);"),                                                   # unknown struct
+    ("mphsir_fn_e", "double mphsir_fn_e(int kid);"),                                                                                   # unknown return type
+    ("mphsir_fn_f", "int mphsir_fn_f(float taps[9]);"),                                                                                # array argument
+])
+def test_parser_refuses_what_it_does_not_model(name, text):
+    import mp_hsir_amd._lib as L
+    with pytest.raises(RuntimeError, match=r"mphsir\.h: %s: cannot bind" % name):
+        L.parse_header(GOOD_HEADER + text)
+
+
+def test_the_header_is_read_once_per_process(lib, monkeypatch):
+    import mp_hsir_amd._lib as L
+    monkeypatch.setattr(L, "_HEADER", "/nonexistent/mphsir.h")
+    with pytest.raises(RuntimeError, match="not found"):
+        L._read_header()
+    saved = (L._lib, L._is_emu)
+    try:
+        assert L.load(LIB) is not None and L.symbols()            # a second load() binds from the parse of the import, not from the file
+    finally:
+        L._lib, L._is_emu = saved

@@ -1,7 +1,6 @@
 """The SSIM loss term without a GPU: the data-parallel engine at world_size 2 over gloo with SpectralLoss(ssim=) (the kernels through the
 CPU-emulated build) against a single-process float64 restatement of the loss on the full batch with torch.optim.AdamW, the flag,
-SpectralLoss's constructor and weights(), the checkpoint helpers of train.py, and the built kernels and the args struct (meta)."""
-import ctypes
+SpectralLoss's constructor and weights(), the checkpoint helpers of train.py, and the built kernels (meta)."""
 import importlib
 import os
 import subprocess
@@ -129,7 +128,7 @@ def test_checkpoints_carry_the_ssim_weight_and_resume_names_it_only_when_a_side_
     assert "trained with loss weights sam 0.1 sdiff 0.05, this run continues with sam 0 sdiff 0\n" in capsys.readouterr().out
 
 
-# ---- meta: the built kernels, the args struct ---------------------------------------------------------------------------------------------
+# ---- meta: the built kernels (the args struct: tests/test_cabi.py) ----------------------------------------------------------------------
 def test_kernels_exist_and_do_not_spill():
     ks = meta.kernels_by_name("arena")
     for name in ("mphsir::ssim_loss_kernel", "mphsir::ssim_loss_finish_kernel"):
@@ -142,17 +141,3 @@ def test_kernels_exist_and_do_not_spill():
     k = ks["mphsir::ssim_loss_kernel"][0]
     assert k.get("group_segment_fixed_size", 0) <= 64 * 1024 and k.get("vgpr_count", 0) + k.get("agpr_count", 0) <= 256, k
 
-
-def test_the_args_struct_matches_its_ctypes_image():
-    import mp_hsir_amd._lib as L
-    want = meta.header_struct("mphsir_ssim_loss_args")
-    got = list(L.SsimLossArgs._fields_)
-    assert [n for n, _ in got] == [n for n, _ in want], (got, want)
-    for (n, tg), (_, tw) in zip(got, want):
-        assert ctypes.sizeof(tg) == ctypes.sizeof(tw) and (tg is ctypes.c_float) == (tw is ctypes.c_float), (n, tg, tw)
-    assert want[0] == ("struct_size", ctypes.c_uint32) and L.SsimLossArgs().struct_size == ctypes.sizeof(L.SsimLossArgs)
-    assert [n for n, _ in want][1:] == ["y", "clean", "grad", "base_loss", "out", "workspace", "workspace_bytes", "B", "C", "H", "W", "w_ssim", "accumulate"]
-    assert {"mphsir_ssim_loss", "mphsir_ssim_loss_workspace_bytes"} <= set(L.symbols())
-    assert "mphsir_ssim_loss_args" in open(os.path.join(meta.ROOT, "INTEGRATION.md")).read()
-    ids = dict(__import__("re").findall(r"#define (MPHSIR_K_\w+) (\d+)", meta.header_text()))
-    assert ids["MPHSIR_K_COUNT"] == "41", "the SSIM pair launches under the ids of the spectral-loss pair"
