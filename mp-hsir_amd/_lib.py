@@ -99,14 +99,40 @@ globals().update({cls.__name__: cls for cls in STRUCTS.values()})      # GemmArg
 TN_GROUP_MAX = CONSTANTS["MPHSIR_TN_GROUP_MAX"]
 REDUCE_MAX_SEGS = CONSTANTS["MPHSIR_REDUCE_MAX_SEGS"]
 
+# Additions to the ABI: headers beside mphsir.h that include it and declare entry points added after its surface was frozen by count
+# (tests/test_cabi.py pins the entry points, structs and kernel ids of mphsir.h itself).  The same parser, tables of their own.
+_ADDITIONS = ("mphsir_accum.h",)
+
+
+def _read_additions():
+    structs, protos = {}, {}
+    for name in _ADDITIONS:
+        path = os.path.join(os.path.dirname(_HEADER), name)
+        if not os.path.exists(path):
+            raise RuntimeError("mp-hsir_amd: header %s not found -- the binding is read from it" % path)
+        with open(path) as f:
+            s, p, _ = parse_header(f.read())
+        structs.update(s)
+        protos.update(p)
+    return structs, protos
+
+
+ADDED_STRUCTS, _ADDED_SYMBOLS = _read_additions()      # mphsir_multi_accum_args / mphsir_multi_accum
+globals().update({cls.__name__: cls for cls in ADDED_STRUCTS.values()})      # MultiAccumArgs
+
 
 def symbols():
     """Every entry point include/mphsir.h declares (checked by tests/test_cabi.py)."""
     return sorted(_SYMBOLS)
 
 
+def added_symbols():
+    """Every entry point the addition headers declare (include/mphsir_accum.h; checked by tests/test_accum_host.py)."""
+    return sorted(_ADDED_SYMBOLS)
+
+
 def _bind(lib):
-    for name, (res, args) in _SYMBOLS.items():
+    for name, (res, args) in list(_SYMBOLS.items()) + list(_ADDED_SYMBOLS.items()):
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

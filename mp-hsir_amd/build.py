@@ -28,7 +28,8 @@ def sources():
 
 def _headers_mtime():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hs.append(os.path.join(os.path.dirname(HERE), "include", "mphsir.h"))
+    inc = os.path.join(os.path.dirname(HERE), "include")
+    hs += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]      # mphsir.h and its additions (mphsir_accum.h)
     return max(os.path.getmtime(h) for h in hs)
 
 

@@ -9,6 +9,7 @@
 //    (host: engine.PackPlan); index < 0 = zero padding.  Runs right after flat_adamw inside the captured step.
 #include <stdlib.h>
 
+#include "../../include/mphsir_accum.h"
 #include "mphsir_host.h"
 #include "mphsir_planar.h"
 
@@ -122,6 +123,41 @@ __global__ __launch_bounds__(256) void multi_copy_kernel(const long* __restrict_
     }
 }
 
+// multi_accum: the same hand-over for gradient accumulation (K micro-batches per optimizer step): micro index 0 stores (dst is not
+// read: whatever the arena held, a NaN included, is overwritten, so nothing is ever zero-filled), index >= 1 adds, one fp32 addition per
+// element (no multiply anywhere: nothing a compiler could contract).  The index comes from the host or -- a captured launch that
+// serves every micro-batch of a group -- from a device int32; either way it is the same for the whole grid: a scalar load and a
+// scalar branch.  Table, blocks, row search, the 16-byte / per-element paths and the tail are multi_copy's; every dst element belongs
+// to exactly one thread, so the result does not depend on the geometry.
+// Bounds: exactly multi_copy's -- a block touches elements [e0, e1) of its row only, e1 <= n.
+__global__ __launch_bounds__(256) void multi_accum_kernel(const long* __restrict__ table, int nseg, int micro, const int* __restrict__ micro_dev) {
+    const int m = micro_dev != nullptr ? *micro_dev : micro;
+    const long b = blockIdx.x;
+    int lo = 0, hi = nseg - 1;                               // the last row whose first block is <= b (wave-uniform: scalar loads)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[4 * mid + 3] <= b) lo = mid; else hi = mid - 1;
+    }
+    const float* src = reinterpret_cast<const float*>(table[4 * lo]);
+    float* dst = reinterpret_cast<float*>(table[4 * lo + 1]);
+    const long n = table[4 * lo + 2], e0 = (b - table[4 * lo + 3]) * MC_BLOCK;
+    const long e1 = e0 + MC_BLOCK < n ? e0 + MC_BLOCK : n;
+    const bool vec = (((unsigned long)src | (unsigned long)dst) & 15) == 0;
+    const long t0 = vec ? e0 + ((e1 - e0) & ~3L) : e0;       // where the per-element part begins
+    if (m <= 0) {
+        if (vec)
+            for (long e = e0 + 4 * threadIdx.x; e + 4 <= e1; e += 1024) *reinterpret_cast<f32x4*>(dst + e) = *reinterpret_cast<const f32x4*>(src + e);
+        for (long e = t0 + threadIdx.x; e < e1; e += 256) dst[e] = src[e];
+    } else {
+        if (vec)
+            for (long e = e0 + 4 * threadIdx.x; e + 4 <= e1; e += 1024) {
+                const f32x4 d = *reinterpret_cast<const f32x4*>(dst + e), s = *reinterpret_cast<const f32x4*>(src + e);
+                *reinterpret_cast<f32x4*>(dst + e) = d + s;
+            }
+        for (long e = t0 + threadIdx.x; e < e1; e += 256) dst[e] = dst[e] + src[e];
+    }
+}
+
 // l1_clamp_loss: the training loss of the reference (train.py:58-61: clamp(restored, 0, 1), nn.L1Loss) and its gradient in one
 // pass: part[block] = sum |clamp(y) - c| / n over the block's elements, g = sign(clamp(y) - c) * [0 <= y <= 1] / n (clamp's
 // autograd passes the gradient where 0 <= y <= 1, bounds included; sign(0) = 0).  The caller sums the partials in order.
@@ -165,6 +201,19 @@ extern "C" int mphsir_multi_copy(const int64_t* table_dev, int32_t nseg, int64_t
     static_assert(sizeof(long) == sizeof(int64_t), "table rows are 64-bit");
     MPHSIR_LAUNCH(MPHSIR_K_MULTI_COPY, multi_copy_kernel, dim3((unsigned)total_blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                   reinterpret_cast<const long*>(table_dev), (int)nseg);
+    return MPHSIR_OK;
+}
+
+extern "C" int mphsir_multi_accum(const mphsir_multi_accum_args* a, void* stream) {
+    using namespace mphsir;
+    clear_error();
+    MPHSIR_CHECK_ARGS(a, "multi_accum");
+    MPHSIR_REQUIRE(a->table_dev && a->nseg > 0, "multi_accum: a null table or no rows (nseg %d)", a->nseg);
+    MPHSIR_REQUIRE(a->total_blocks > 0 && a->total_blocks < (1LL << 31), "multi_accum: total_blocks %lld outside 1 .. 2^31 - 1", (long long)a->total_blocks);
+    MPHSIR_REQUIRE(a->micro >= 0, "multi_accum: micro index %d is negative", a->micro);
+    // under the hand-over's id: the launch timer reports the family (as the SSIM pair launches under the spectral-loss ids), MPHSIR_K_COUNT stays
+    MPHSIR_LAUNCH(MPHSIR_K_MULTI_COPY, multi_accum_kernel, dim3((unsigned)a->total_blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                  reinterpret_cast<const long*>(a->table_dev), (int)a->nseg, (int)a->micro, reinterpret_cast<const int*>(a->micro_dev));
     return MPHSIR_OK;
 }
 

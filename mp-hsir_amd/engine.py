@@ -212,8 +212,22 @@ def _external_events_work(dev):
 class DataParallelEngine:
     def __init__(self, net, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, bucket_mb=32, process_group=None,
                  loss_fn=l1_after_clamp, use_graph=False, graph_warmup=2, use_pack_plan=True, loss_scaling="auto",
-                 init_scale=65536.0, growth_interval=2000, grad_clip=None, ema_decay=None, ema_warmup=True):
+                 init_scale=65536.0, growth_interval=2000, grad_clip=None, ema_decay=None, ema_warmup=True, accum_steps=1):
         self.net, self.lr, self.betas, self.eps, self.wd = net, lr, betas, eps, weight_decay
+        # Gradient accumulation, off at 1 (then train_step is what it always was).  accum_steps = K > 1: train_step is still called once per
+        # micro-batch and returns that micro-batch's loss; calls 0 .. K-2 of a group run forward, loss, backward and the ACCUMULATING
+        # hand-over (ops.MultiCopy(micro=): index 0 stores, index >= 1 adds -- the arena is never zero-filled), call K-1 also the optimizer
+        # with grad_scale 1 / (world K) and plan.refresh().  step_count counts optimizer steps.  TVSP couples the samples of a batch
+        # (SURVEY Q1), so K micro-batches of B are not one batch of K B: they are exactly what K data-parallel ranks compute, with the mean
+        # over ranks replaced by the mean over micro-batches (at K = 2 bitwise: one fp32 addition is commutative).
+        if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
+            raise ValueError("accum_steps must be an integer >= 1 (1: off), got %r" % (accum_steps,))
+        self.accum_steps = accum_steps
+        self._micro = 0                 # index of the next micro-batch within its group
+        self._micro_arg = None          # what _gather_bucket hands to the hand-over: None (off), the host index, or the staged device int32
+        self._group_graph = False       # the mode of the open group: eager <-> graph switches at a group boundary only
+        self.group_loss = None          # device 0-d fp32: ((l_0 + l_1) + ... + l_{K-1}) * fp32(1 / K) of the last completed group
+        self._loss_acc = self._inv_k = self._micro_dev = None
         self.loss_fn = loss_fn
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
@@ -249,8 +263,8 @@ class DataParallelEngine:
         # with fp32 powf; a replayed step reads [lr, 1 - beta1^t, sqrt(1 - beta2^t)] that the host formed in float64 (1 - 0.9f = 0.100000024
         # against fp32(1 - 0.9) = 0.1 at t = 1): eager and graph mode differ in the last bits from the first replayed step on.  That is what
         # the default path has always computed and it stays.  Under a SpectralLoss the eager step stages the same scalars on the device, so
-        # that eager and graph mode train bitwise the same parameters.
-        self._eager_hyper = isinstance(loss_fn, SpectralLoss)
+        # that eager and graph mode train bitwise the same parameters.  So does every step of an accumulating engine, under every loss.
+        self._eager_hyper = isinstance(loss_fn, SpectralLoss) or accum_steps > 1
         if self.world > 1:     # DDP's initial parameter broadcast (rank 0 -> all), one flat message
             ps = [p for p in net.parameters()]
             flat = torch.cat([p.data.reshape(-1).float() for p in ps])
@@ -299,7 +313,11 @@ class DataParallelEngine:
             self._gn_ws = ops.grad_norm_workspace(self.flat_g)
         # built here, outside any capture: its pinned tables cannot be allocated while a stream is capturing (a capture at the
         # very first hand-over -- graph_warmup=1 -- would otherwise be invalidated)
-        self._multi_copy = ops.MultiCopy(self.flat_g.device, len(used)) if used else None
+        if self.accum_steps > 1:
+            # a captured micro-step takes one table per bucket; the accumulating hand-over has no fall-back when they run out
+            self._multi_copy = ops.MultiCopy(self.flat_g.device, len(used), capture_tables=max(24, 2 * len(self.buckets)))
+        else:
+            self._multi_copy = ops.MultiCopy(self.flat_g.device, len(used)) if used else None
         self._gviews = [self.flat_g[o:o + p.numel()].view(p.shape) for p, o in zip(used, offs)]
         self._bucket_members = []            # per bucket: (params, arena views)
         bi = 0
@@ -347,6 +365,22 @@ class DataParallelEngine:
         # through the multi-tensor kernel, the rest are copied one by one; a gradient that already is the arena view
         # needs no copy at all.
         fv, fg = [], []
+        if self.accum_steps > 1:
+            # accumulating hand-over: the micro index (the host's in an eager step, the staged device int32 under capture) decides between
+            # store and add INSIDE the launch -- a host branch could not live in a captured graph -- so everything rides in the one table:
+            # a gradient that is not contiguous fp32 is first made so (a temporary; `v.copy_(g)` would overwrite the sum)
+            for p, v in zip(ps, views):
+                g = p.grad
+                if g is None:
+                    continue
+                assert g.data_ptr() != v.data_ptr(), "accum_steps > 1: a gradient that already is its arena view cannot be accumulated"
+                fv.append(v)
+                fg.append(g if g.is_contiguous() and g.dtype == v.dtype else g.to(v.dtype).contiguous())
+            if fv:
+                self._multi_copy(fv, fg, micro=self._micro_arg, micro_hint=self._micro)
+            for p in ps:
+                p.grad = None
+            return
         for p, v in zip(ps, views):
             g = p.grad
             if g is None or g.data_ptr() == v.data_ptr():
@@ -378,6 +412,8 @@ class DataParallelEngine:
             self._remaining[bi] -= 1
             if self._remaining[bi] == 0:
                 self._gather_bucket(bi)
+                if self._micro < self.accum_steps - 1:
+                    return                                 # accumulation: no communication before the group's last micro-batch (DDP's no_sync)
                 s, e, _ = self.buckets[bi]
                 self._pending.append(dist.all_reduce(self.flat_g[s:e], group=self.pg, async_op=True))
         return hook
@@ -423,8 +459,9 @@ class DataParallelEngine:
         return loss
 
     def _optimizer_step(self, lr, hyper=None):
-        """AdamW over the arenas (1/world folded in); fp16 path: non-finite check + unscale + skip + scale update"""
-        gs = 1.0 / self.world
+        """AdamW over the arenas (1/world folded in -- 1/(world K) when K micro-batches were accumulated: the mean gradient over all of
+        them); fp16 path: non-finite check + unscale + skip + scale update"""
+        gs = 1.0 / (self.world * self.accum_steps)
         if self.grad_clip is not None or self.ema_decay is not None:
             # grad_check (scaler) -> grad_norm (clip) -> flat_adamw_ex -> scaler_update (scaler): plain launches, captured with the step.
             # grad_scale stays 1 / world: the norm is that of the mean gradient.  Without a scaler (bf16, fp32) a norm that is not finite
@@ -525,35 +562,166 @@ class DataParallelEngine:
         self._stage_hyper(self._hyper_values(self.lr if lr is None else lr, self.step_count))
         self._graph.replay()
         if self.world > 1:
-            if getattr(self, "_overlap", False) and len(self._bucket_order) == len(self.buckets):
-                handles, issued = [], set()
-                try:
-                    for bi in self._bucket_order:           # completion order of the captured backward
-                        self._comm.wait_event(self._bucket_events[bi])
-                        st, en, _ = self.buckets[bi]
-                        with torch.cuda.stream(self._comm):
-                            handles.append(dist.all_reduce(self.flat_g[st:en], group=self.pg, async_op=True))
-                        issued.add(bi)
-                    for h in handles:
-                        h.wait()
-                    torch.cuda.current_stream(dev).wait_stream(self._comm)
-                except Exception as e:      # a stack that cannot do this: finish the step the plain way and stop trying
-                    import warnings
-                    warnings.warn("graph-mode all-reduce overlap disabled (%s: %s)" % (type(e).__name__, e))
-                    self._overlap = False
-                    for h in handles:
-                        h.wait()
-                    torch.cuda.synchronize(dev)
-                    for bi in range(len(self.buckets)):
-                        if bi not in issued:
-                            st, en, _ = self.buckets[bi]
-                            dist.all_reduce(self.flat_g[st:en], group=self.pg)
-            else:
-                dist.all_reduce(self.flat_g, group=self.pg)     # no external events on this stack: one message after the replay
+            self._allreduce_after_replay(dev)
             self._optimizer_step(None, hyper=self._hyper)
             if self.plan is not None:
                 self.plan.refresh()
         return self._sloss
+
+    def _allreduce_after_replay(self, dev):
+        """world > 1, graph mode: the gradient all-reduce behind a replay -- per bucket, started while the replay is still running, where
+        the stack has external events; else one message"""
+        if getattr(self, "_overlap", False) and len(self._bucket_order) == len(self.buckets):
+            handles, issued = [], set()
+            try:
+                for bi in self._bucket_order:           # completion order of the captured backward
+                    self._comm.wait_event(self._bucket_events[bi])
+                    st, en, _ = self.buckets[bi]
+                    with torch.cuda.stream(self._comm):
+                        handles.append(dist.all_reduce(self.flat_g[st:en], group=self.pg, async_op=True))
+                    issued.add(bi)
+                for h in handles:
+                    h.wait()
+                torch.cuda.current_stream(dev).wait_stream(self._comm)
+            except Exception as e:      # a stack that cannot do this: finish the step the plain way and stop trying
+                import warnings
+                warnings.warn("graph-mode all-reduce overlap disabled (%s: %s)" % (type(e).__name__, e))
+                self._overlap = False
+                for h in handles:
+                    h.wait()
+                torch.cuda.synchronize(dev)
+                for bi in range(len(self.buckets)):
+                    if bi not in issued:
+                        st, en, _ = self.buckets[bi]
+                        dist.all_reduce(self.flat_g[st:en], group=self.pg)
+        else:
+            dist.all_reduce(self.flat_g, group=self.pg)     # no external events on this stack: one message after the replay
+
+    # ---- gradient accumulation (accum_steps > 1) ------------------------------------------------------------------------------------------
+    _MICRO_SLOTS = 4
+
+    def _stage_micro(self, j):
+        """the micro index of this call -> the device int32 the captured hand-over and loss sum read: a ring of pinned slots, one event per
+        slot, as _stage_hyper stages the optimizer's scalars (no host synchronisation)"""
+        ring = getattr(self, "_micro_ring", None)
+        if ring is None:
+            ring = self._micro_ring = [torch.zeros(self._MICRO_SLOTS, dtype=torch.int32).pin_memory(), [None] * self._MICRO_SLOTS, 0]
+        host, events, turn = ring
+        k = turn % self._MICRO_SLOTS
+        ring[2] = turn + 1
+        if events[k] is not None:
+            events[k].synchronize()
+        host[k] = int(j)
+        self._micro_dev.copy_(host[k], non_blocking=True)
+        events[k] = torch.cuda.Event()
+        events[k].record()
+
+    def _sum_loss(self, loss, micro):
+        """the running loss sum of the open group, on the device, fp32 additions in ascending order: the sum IS l_0 at index 0 (nothing is
+        zero-filled), sum + l_j after.  micro: the host index, or the staged device int32 (under capture: the choice is made on the device)"""
+        loss = loss.detach().float().reshape(())
+        if isinstance(micro, torch.Tensor):
+            self._loss_acc.copy_(torch.where(micro == 0, loss, self._loss_acc + loss))
+        elif micro == 0:
+            self._loss_acc.copy_(loss)
+        else:
+            self._loss_acc.add_(loss)
+
+    def _micro_step_eager(self, degraded, clean, prompt, j):
+        """forward, loss, backward and the accumulating hand-over of micro-batch j with eager launches"""
+        first = self.arena is None
+        last = j == self.accum_steps - 1
+        hooks = self.world > 1 and not self.use_graph        # the bucket hooks gather (and, on the last micro-batch, start their all-reduce)
+        if not first and hooks:
+            self._remaining = [b[2] for b in self.buckets]
+        self._micro_arg = j
+        restored = self.net(degraded, prompt)
+        loss = self._loss_backward(restored, clean)
+        if not first and not hooks:
+            for bi in range(len(self.buckets)):
+                self._gather_bucket(bi)
+            if self.world > 1 and last:
+                for s, e, _ in self.buckets:
+                    self._pending.append(dist.all_reduce(self.flat_g[s:e], group=self.pg, async_op=True))
+        if first:
+            assert j == 0
+            self._build_arenas()        # flat_g = the gradients of micro-batch 0: the store of index 0
+            self._apply_resume()
+        if self._loss_acc is None:
+            self._loss_acc = torch.zeros((), dtype=torch.float32, device=self.flat_p.device)
+            self._inv_k = torch.tensor(1.0 / self.accum_steps, dtype=torch.float32, device=self.flat_p.device)
+        self._sum_loss(loss, j)
+        return loss.detach()
+
+    def _micro_step_graph(self, degraded, clean, prompt, j):
+        """the same through ONE captured graph, replayed for every micro-batch of every group: the hand-over and the loss sum read the
+        micro index from a device int32 staged per call, so nothing is captured again when it changes.  The optimizer and plan.refresh()
+        are plain launches behind the last replay of a group (train_step), where world > 1 has always had them."""
+        dev = degraded.device
+        key = self._capture_key(degraded, clean, prompt)
+        if self._graph is not None and key != self._graph_key:
+            self._graph = None                              # another batch shape / dtype / mode: capture again (as _train_step_graph does)
+            self._multi_copy.recycle()                      # the dropped graph's pointer tables are free again
+        if self._graph is None:
+            self._graph_key = key
+            self._sx, self._sc, self._sp = degraded.clone(), clean.clone(), prompt.clone()
+            self._hyper = torch.zeros(4 if self.ema_decay is not None else 3, dtype=torch.float32, device=dev)
+            if self._micro_dev is None:
+                self._micro_dev = torch.zeros((), dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                self._micro_arg = self._micro_dev
+                restored = self.net(self._sx, self._sp)
+                overlap = self.world > 1 and getattr(self, "_overlap", False)
+                if overlap:
+                    self._remaining = [b[2] for b in self.buckets]
+                    self._bucket_order, self._capturing = [], True
+                try:
+                    loss = self._loss_backward(restored, self._sc)
+                finally:
+                    self._capturing = False
+                for bi in range(len(self.buckets)):
+                    if not (overlap and bi in self._bucket_order):
+                        self._gather_bucket(bi)
+                self._sloss = loss.detach()
+                self._sum_loss(self._sloss, self._micro_dev)
+            self._graph = g
+        assert self._sx.shape == degraded.shape and self._sc.shape == clean.shape and self._sp.shape == prompt.shape
+        self._sx.copy_(degraded)
+        self._sc.copy_(clean)
+        self._sp.copy_(prompt)
+        self._stage_micro(j)
+        self._graph.replay()
+        if self.world > 1 and j == self.accum_steps - 1:
+            self._allreduce_after_replay(dev)
+        return self._sloss
+
+    def _train_step_accum(self, degraded, clean, prompt, lr):
+        K, j = self.accum_steps, self._micro
+        if j == 0:
+            self._group_graph = bool(self.use_graph and not self.force_eager and self.arena is not None
+                                     and self.step_count >= self.graph_warmup and degraded.is_cuda)
+        loss = (self._micro_step_graph if self._group_graph else self._micro_step_eager)(degraded, clean, prompt, j)
+        if j < K - 1:
+            self._micro = j + 1
+            return loss
+        for h in self._pending:
+            h.wait()
+        self._pending = []
+        self.step_count += 1
+        values = self._hyper_values(self.lr if lr is None else lr, self.step_count)
+        if self._group_graph:
+            self._stage_hyper(values)
+            hyper = self._hyper
+        else:
+            hyper = torch.tensor(values, dtype=torch.float32, device=self.flat_p.device)
+        self._optimizer_step(None, hyper=hyper)
+        if self.plan is not None:
+            self.plan.refresh()
+        self.group_loss = self._loss_acc * self._inv_k
+        self._micro = 0
+        return loss
 
     # ---- optimizer state for checkpoints (the reference's Lightning checkpoints carry AdamW's moments and step) ----------
     def optimizer_state(self):
@@ -680,6 +848,8 @@ class DataParallelEngine:
     def train_step(self, degraded, clean, prompt, lr=None):
         if self.use_pack_plan and self.plan is None and self.arena is not None:
             self.plan = PackPlan(self.flat_p).build()      # caches were populated by the step(s) before
+        if self.accum_steps > 1:
+            return self._train_step_accum(degraded, clean, prompt, lr)
         if (self.use_graph and not self.force_eager and self.arena is not None and self.step_count >= self.graph_warmup
                 and degraded.is_cuda):
             return self._train_step_graph(degraded, clean, prompt, lr)

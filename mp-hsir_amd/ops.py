@@ -420,10 +420,14 @@ class MultiCopy:
     """dsts[i].copy_(srcs[i]) for lists of contiguous fp32 tensors in ONE launch (mphsir_multi_copy): the table of pointers is
     written into a pinned host buffer (a small ring of them: an eager caller may run a step ahead of the GPU) and copied to the
     device on the launch stream -- under hipGraph capture that copy is a node that re-reads the same pinned rows on every replay,
-    and the captured pointers stay valid because a graph's allocations live in its private pool."""
+    and the captured pointers stay valid because a graph's allocations live in its private pool.
+
+    micro (gradient accumulation, engine.DataParallelEngine(accum_steps=K)): None -- that launch, as ever.  An int or a device int32
+    tensor: the accumulate form, mphsir_multi_accum over the same table -- index 0 stores (dsts are not read), index >= 1 adds; a tensor
+    is read by the launch, so one captured call serves every micro-batch of a group."""
     BLOCK = 4096
 
-    def __init__(self, device, capacity, ring=4):
+    def __init__(self, device, capacity, ring=4, capture_tables=24):
         self.device, self.capacity, self.ring = device, capacity, ring
         self.host = [torch.empty((capacity, 4), dtype=torch.int64).pin_memory() if device.type == "cuda" else torch.empty((capacity, 4), dtype=torch.int64)
                      for _ in range(ring)]
@@ -434,16 +438,33 @@ class MultiCopy:
         # pair is never reused -- and pinned memory cannot be allocated while a stream is capturing, so they are set aside here
         pin = device.type == "cuda"
         self.for_capture = [(torch.empty((capacity, 4), dtype=torch.int64).pin_memory() if pin else torch.empty((capacity, 4), dtype=torch.int64),
-                             torch.empty((capacity, 4), dtype=torch.int64, device=device)) for _ in range(24)]
+                             torch.empty((capacity, 4), dtype=torch.int64, device=device)) for _ in range(capture_tables)]
         self.captured = []
 
-    def __call__(self, dsts, srcs):
+    def recycle(self):
+        """the graphs that captured calls of this object are gone: their table pairs may be captured again"""
+        self.for_capture += self.captured
+        self.captured = []
+
+    def __call__(self, dsts, srcs, micro=None, micro_hint=None):
         n = len(dsts)
         if n == 0:
             return
         assert n <= self.capacity
+        micro_dev = None
+        if isinstance(micro, torch.Tensor):
+            assert micro.dtype == torch.int32 and micro.numel() == 1 and micro.device.type == self.device.type, "multi_accum: the device micro index is one int32 on the launch device"
+            micro_dev, micro = micro, 0
+        elif micro is not None:
+            micro = int(micro)
+            assert micro >= 0, "multi_accum: micro index %d is negative" % micro
         capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
         if capturing:
+            if not self.for_capture and micro is not None:
+                # the copy form falls back to the framework's multi-tensor copy below; an accumulate form of it would need a host
+                # branch on the micro index, which a captured graph cannot hold
+                raise RuntimeError("mp-hsir_amd: MultiCopy has no pointer table left for an accumulating hand-over under graph capture "
+                                   "(%d captured so far): build it with capture_tables >= the hand-overs of one captured step" % len(self.captured))
             if not self.for_capture:          # more captured hand-overs than tables set aside: the framework's multi-tensor copy
                 torch._foreach_copy_(list(dsts), list(srcs))
                 return
@@ -462,11 +483,23 @@ class MultiCopy:
             blk += (ne + self.BLOCK - 1) // self.BLOCK
         h[:n] = torch.tensor(rows, dtype=torch.int64)
         dv[:n].copy_(h[:n], non_blocking=True)
-        _lib.check(_lib.load().mphsir_multi_copy(_p(dv), n, blk, _stream(dv)), "multi_copy")
+        if micro is None:
+            _lib.check(_lib.load().mphsir_multi_copy(_p(dv), n, blk, _stream(dv)), "multi_copy")
+        else:
+            _check(dv, micro_dev)
+            a = _lib.MultiAccumArgs(table_dev=_p(dv), nseg=n, total_blocks=blk, micro=micro, micro_dev=_p(micro_dev))
+            _lib.check(_lib.load().mphsir_multi_accum(ctypes.byref(a), _stream(dv)), "multi_accum")
         if self.device.type == "cuda" and not capturing:
             self.events[k] = torch.cuda.Event()
             self.events[k].record()
-        _acct("multi_copy", 0.0, 8.0 * sum(d.numel() for d in dsts))
+        ne = sum(d.numel() for d in dsts)
+        if micro is None:
+            _acct("multi_copy", 0.0, 8.0 * ne)
+        else:
+            # index 0 reads src and writes dst; from index 1 on dst is read as well and every element costs one addition.  A device index
+            # is not known here: the caller's hint, else the read-modify-write form
+            adds = (micro if micro_dev is None else 1 if micro_hint is None else int(micro_hint)) >= 1
+            _acct("multi_accum", float(ne) if adds else 0.0, (12.0 if adds else 8.0) * ne)
 
 
 def _l1_clamp_loss_launch(y, clean, want_grad):

@@ -7,7 +7,7 @@ Like the reference, the namespace is built at import time (`from options import 
 unknown flags are tolerated so that importing this module under pytest/torchrun does not abort.
 Additions (not present in the reference, all optional): --model, --precision, --steps_per_epoch, --graph,
 --synthetic, --log_every, --allow_surrogate_clip, --all_sources, --resume, --fused_degrade, --scene_dir, --crop_jitter, --grad_clip, --ema_decay, --task_classes, --cassi_mask, --cassi_step, --loss_sam, --loss_sdiff, --loss_ssim, --val_dir, --val_every, --val_patch, --val_crops, --val_batch, --val_modes, --val_seed, --val_weights,
---save_best.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
+--save_best, --accum_steps.  Reference hazards kept on purpose: `--num_gpus type=list` turns "01"
 into ['0','1'] (options.py:36) and `--classifier type=bool` treats any non-empty string as True.
 --fused_degrade 1 works at every --patch_size: a patch of up to 128 x 128 is degraded by the plane form of the launch, a larger one (256
 out of a --scene_dir store, say) by its tiled form, with the same plan and the same element values.
@@ -85,6 +85,10 @@ _FLAGS = [
     ("--val_weights", dict(type=str, default="auto", choices=["auto", "ema", "raw"], help="the weights a pass scores: auto = the EMA weights "
                            "under --ema_decay, else the current ones")),
     ("--save_best", dict(type=int, default=0, help="1 (with --ckpt_dir): write best.ckpt whenever the mean validation PSNR improves")),
+    ("--accum_steps", dict(type=int, default=1, help="K > 1: gradient accumulation, K micro-batches of --batch_size per optimizer step (the gradients "
+                           "summed on the device, one AdamW step on their mean).  K micro-batches equal K data-parallel ranks, not one batch of "
+                           "K * batch_size, because TVSP couples the samples of a batch; the learning rate is the user's to scale, as with more "
+                           "GPUs.  An epoch takes steps_per_epoch // K optimizer steps; --log_every counts them.  1 (default): off")),
 ]
 
 

@@ -20,6 +20,9 @@ key and shape match, epoch 0); --resume 1 additionally restores the optimizer st
 differences to the loss (engine.SpectralLoss); the log line then ends with the unweighted terms, checkpoints carry the weights as
 `mphsir_loss` and --resume 1 says so when the run's weights differ from the file's.  --loss_ssim F (0 by default) adds F * (1 - SSIM), the
 band-wise 7 x 7 SSIM the evaluation reports, by a launch pair of its own; the log line then also ends with ` ssim S`.
+--accum_steps K (1 by default: off) takes one optimizer step per K batches (engine.DataParallelEngine(accum_steps=K)): K micro-batches are
+what K data-parallel ranks compute, not one batch of K * batch_size; `it` and --log_every then count optimizer steps and `train_loss` is the
+mean loss of the group.
 --val_every E --val_dir DIR (0 by default: off) scores held-out crops after every E-th epoch and after the last (validate.py: the crops and
 their degraded forms of test.py's modes stay on the device, a pass reads back one small table); rank 0 prints `val epoch E mode M psnr ..
 ssim .. sam .. n ..` per mode and `val epoch E mean ...`, --save_best 1 writes <ckpt_dir>/best.ckpt whenever the mean PSNR improves, and
@@ -91,6 +94,9 @@ def load_warm_start(net, path, device, engine=None, resume=False):
             named = "ssim" in was or "ssim" in now                    # the SSIM weight is named only when either side has one
             said = ["sam %g sdiff %g" % (w["sam"], w["sdiff"]) + (" ssim %g" % w.get("ssim", 0.0) if named else "") for w in (was, now)]
             print("note: the checkpoint was trained with loss weights %s, this run continues with %s" % tuple(said), flush=True)
+        was_k, now_k = int(ckpt.get("accum_steps", 1)), getattr(engine, "accum_steps", 1)
+        if was_k != now_k:
+            print("note: the checkpoint was trained with --accum_steps %d, this run continues with --accum_steps %d" % (was_k, now_k), flush=True)
     return len(kept), resume_epoch
 
 
@@ -108,6 +114,8 @@ def save_checkpoint(path, net, engine, epoch, val=None):
     ckpt = {"state_dict": {"net." + k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, "epoch": epoch,
             "mphsir_optimizer": engine.optimizer_state(), "mphsir_clip_prompt": net.clip_prompts.detach().cpu().clone(),
             "mphsir_clip_source": net.text_prompt.clip_source, "mphsir_loss": loss_weights(engine)}
+    if getattr(engine, "accum_steps", 1) > 1:      # written at epoch ends: a group is never open in a checkpoint
+        ckpt["accum_steps"] = engine.accum_steps
     if getattr(engine, "ema_decay", None) is not None:
         ckpt["state_dict_ema"] = {"net." + k: v.detach().cpu().clone() for k, v in engine.ema_state_dict().items()}
     if val is not None:
@@ -159,9 +167,11 @@ def main():
     extras = opt.grad_clip > 0 or opt.ema_decay > 0
     if opt.loss_sam < 0 or opt.loss_sdiff < 0 or opt.loss_ssim < 0:
         raise SystemExit("--loss_sam / --loss_sdiff / --loss_ssim must be >= 0 (0: the term is off)")
+    if opt.accum_steps < 1:
+        raise SystemExit("--accum_steps must be >= 1 (1: off), got %d" % opt.accum_steps)
     spectral = opt.loss_sam > 0 or opt.loss_sdiff > 0 or opt.loss_ssim > 0      # off: the engine's default loss, the launches and the log lines of always
     eng = DataParallelEngine(net, lr=opt.lr, use_graph=bool(opt.graph), grad_clip=opt.grad_clip if opt.grad_clip > 0 else (float("inf") if extras else None),     # EMA alone: measure the norm for the log
-                             ema_decay=opt.ema_decay if opt.ema_decay > 0 else None,
+                             ema_decay=opt.ema_decay if opt.ema_decay > 0 else None, **(dict(accum_steps=opt.accum_steps) if opt.accum_steps > 1 else {}),
                              **(dict(loss_fn=SpectralLoss(opt.loss_sam, opt.loss_sdiff, opt.loss_ssim)) if spectral else {}))
     validator = history = None
     if opt.val_every:               # 0 (default): nothing of validate.py is imported or built
@@ -221,13 +231,23 @@ def main():
             db = PatchDB(opt.db_path, dataset_names=None if keep_all else REMOTE_SENSING_SOURCES)
             src = PatchDBSource(db, opt.batch_size, de_types, data_type, dev, opt.seed, rank, world, opt.repeat, fused_degrade=bool(opt.fused_degrade), cassi=cassi)
         steps_per_epoch = src.steps_per_epoch()
+    K = opt.accum_steps
+    if K > 1:
+        # --accum_steps: an epoch draws the source's batches in the order of always, K per optimizer step; a trailing partial group is not
+        # drawn (no group is ever open at an epoch end, where checkpoints are written)
+        if rank == 0 and steps_per_epoch % K:
+            print("note: --accum_steps %d: %d batches per epoch -> %d optimizer steps, %d not drawn" % (K, steps_per_epoch, steps_per_epoch // K, steps_per_epoch % K), flush=True)
+        steps_per_epoch //= K
     for epoch in range(start_epoch, opt.epochs):
         lr = warmup_cosine_lr(epoch, opt.lr, opt.epochs)
         running = 0.0
-        for it in range(steps_per_epoch):
-            _, degraded, clean, prompt = src.next()
-            loss = eng.train_step(degraded, clean, prompt, lr=lr)
+        for it in range(steps_per_epoch):       # optimizer steps
+            for _micro in range(K):
+                _, degraded, clean, prompt = src.next()
+                loss = eng.train_step(degraded, clean, prompt, lr=lr)
             if (it + 1) % opt.log_every == 0:
+                if K > 1:
+                    loss = eng.group_loss.clone()                   # the mean loss of the group's micro-batches, formed on the device
                 if world > 1:
                     dist.all_reduce(loss, op=dist.ReduceOp.AVG)       # self.log(..., sync_dist=True), train.py:65
                 running = float(loss)
