@@ -104,9 +104,9 @@ REDUCE_MAX_SEGS = CONSTANTS["MPHSIR_REDUCE_MAX_SEGS"]
 _ADDITIONS = ("mphsir_accum.h",)
 
 
-def _read_additions():
+def _read_additions(names=_ADDITIONS):
     structs, protos = {}, {}
-    for name in _ADDITIONS:
+    for name in names:
         path = os.path.join(os.path.dirname(_HEADER), name)
         if not os.path.exists(path):
             raise RuntimeError("mp-hsir_amd: header %s not found -- the binding is read from it" % path)
@@ -120,6 +120,11 @@ def _read_additions():
 ADDED_STRUCTS, _ADDED_SYMBOLS = _read_additions()      # mphsir_multi_accum_args / mphsir_multi_accum
 globals().update({cls.__name__: cls for cls in ADDED_STRUCTS.values()})      # MultiAccumArgs
 
+# include/mphsir_bands.h (spectral windows of whole-scene inference): tables of its own, because tests/test_accum_host.py pins the contents
+# of the two above as tests/test_cabi.py pins those of mphsir.h; checked by tests/test_scene_bands_host.py
+BANDS_STRUCTS, _BANDS_SYMBOLS = _read_additions(("mphsir_bands.h",))
+globals().update({cls.__name__: cls for cls in BANDS_STRUCTS.values()})      # SceneGatherBandsArgs, SceneBlendBandsArgs
+
 
 def symbols():
     """Every entry point include/mphsir.h declares (checked by tests/test_cabi.py)."""
@@ -131,8 +136,13 @@ def added_symbols():
     return sorted(_ADDED_SYMBOLS)
 
 
+def bands_symbols():
+    """Every entry point include/mphsir_bands.h declares (checked by tests/test_scene_bands_host.py)."""
+    return sorted(_BANDS_SYMBOLS)
+
+
 def _bind(lib):
-    for name, (res, args) in list(_SYMBOLS.items()) + list(_ADDED_SYMBOLS.items()):
+    for name, (res, args) in list(_SYMBOLS.items()) + list(_ADDED_SYMBOLS.items()) + list(_BANDS_SYMBOLS.items()):
         fn = getattr(lib, name)     # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

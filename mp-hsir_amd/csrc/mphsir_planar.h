@@ -35,6 +35,15 @@ __device__ __forceinline__ int mirror(int y, int n) {
     return m < n ? m : p - m;
 }
 
+// the blend weight w(u) of include/mphsir.h for a tile at origin o of extent t on an axis of extent n; ovp1 = overlap + 1 (scene.hip on
+// the two spatial axes, scene_bands.hip on the band axis as well)
+__device__ __forceinline__ float ramp(int u, int o, int t, int n, float ovp1) {
+    float w = 1.f;
+    if (o > 0) w = fminf(w, (float)(u + 1) / ovp1);
+    if (o + t < n) w = fminf(w, (float)(t - u) / ovp1);
+    return w;
+}
+
 // The eight flip / rotation transforms of degrade.augment (mode m: rot90 counter-clockwise by m / 2, then an up-down flip when m is
 // odd).  Every mode is one index map: element (u, v) of the transformed plane is element (a, b) of the plane with
 //       (p, q) = transposing ? (v, u) : (u, v),   a = fy ? rows - 1 - p : p,   b = fx ? cols - 1 - q : q

@@ -57,14 +57,6 @@ struct BlendDev {
     int ny, nx, C, H, W, th, tw, ov, clamp01;
 };
 
-// w(u) of include/mphsir.h for a tile at origin o of extent t on an axis of extent n; ovp1 = ov + 1
-__device__ __forceinline__ float ramp(int u, int o, int t, int n, float ovp1) {
-    float w = 1.f;
-    if (o > 0) w = fminf(w, (float)(u + 1) / ovp1);
-    if (o + t < n) w = fminf(w, (float)(t - u) / ovp1);
-    return w;
-}
-
 // grid (ceil(H * ceil(W/4) / 256), ceil(C / SCENE_CH))
 __global__ __launch_bounds__(256) void scene_blend_kernel(BlendDev a) {
     const int W4 = (a.W + 3) >> 2;

@@ -4,6 +4,8 @@
 //
 //   d4_gather   tiles [count][C][th][tw] <- mode_g(mirror-cut tile t of scene [C][H][W]) for the items j = g * n_tiles + t of a batch
 //   d4_fold     store [n_tiles][C][th][tw] <- (store or 0) + sum over the batch's items of a tile, in ascending j, of inverse_mode_g(y)
+//   bands_gather  the d4 gather with one more folded coordinate: an item has a band origin too and channel c of it is scene band
+//               mirror(ob + c, Cs) (spectral windows: include/mphsir_bands.h); the same body, origin rows of three
 //
 // Every mode is one index map of the tile (struct D4 of mphsir_planar.h holds the table; a transposing mode has th == tw), and the fold
 // reads y through the same map the other way round.
@@ -22,6 +24,7 @@
 // and its values are folded into the scene by the mirror map, so no access depends on it holding a valid plan (origins within +-2^30).
 #include "mphsir_host.h"
 #include "mphsir_planar.h"
+#include "../../include/mphsir_bands.h"
 
 namespace mphsir {
 
@@ -33,20 +36,27 @@ constexpr int D4_P = D4_S + 1;       // LDS row pitch in dwords
 
 struct D4GatherDev {
     const float* scene; const int* origins; float* tiles;
-    int j0, n_tiles, last, modes, C, H, W, th, tw;
+    int j0, n_tiles, last, modes, C, Cs, H, W, th, tw;      // Cs: the scene's band count (the band form; else C)
 };
 
-// grid (max(ceil(th * tw/4 / 256), ceil(th/32) * ceil(tw/32)), ceil(C / D4_CH), count)
-__global__ __launch_bounds__(256) void d4_gather_kernel(D4GatherDev a) {
-    __shared__ float lds[D4_LC][D4_S][D4_P];
+typedef float (*D4Lds)[D4_S][D4_P];
+
+// The body of both gathers.  `bands` is a literal in each of the two kernels below, so every test of it folds away: false is the d4 gather
+// as it was (origin rows {oy, ox}, channel c of an item is scene band c), true reads rows {ob, oy, ox} and takes channel c from scene
+// band mirror(ob + c, Cs).  The band is a function of the workgroup's indices alone, so its fold is scalar work.
+__device__ __forceinline__ void d4_gather_body(const D4GatherDev& a, D4Lds lds, const bool bands) {
     const int jz = a.j0 + (int)blockIdx.z, j = jz < a.last ? jz : a.last;
     const int g = j / a.n_tiles, t = j - g * a.n_tiles;
     const D4 d4((a.modes >> (3 * g)) & 7);
     const bool fy = d4.fy, fx = d4.fx;
-    const int oy = a.origins[2 * t], ox = a.origins[2 * t + 1];
+    const int* org = a.origins + (bands ? 3 : 2) * t;
+    const int ob = bands ? org[0] : 0, oy = org[bands ? 1 : 0], ox = org[bands ? 2 : 1];
     const int c0 = blockIdx.y * D4_CH;
     const long plane = (long)a.H * a.W, tplane = (long)a.th * a.tw;
-    const float* src = a.scene + c0 * plane;
+    long band[D4_CH];                                             // the scene plane of each channel of the chunk, in floats
+#pragma unroll
+    for (int c = 0; c < D4_CH; ++c) band[c] = (bands ? (long)mirror(ob + c0 + c, a.Cs) : (long)(c0 + c)) * plane;
+    const float* src = a.scene;
     float* dst = a.tiles + ((long)blockIdx.z * a.C + c0) * tplane;
     const int tid = threadIdx.x;
     if (!d4.tr) {
@@ -63,7 +73,7 @@ __global__ __launch_bounds__(256) void d4_gather_kernel(D4GatherDev a) {
 #pragma unroll
         for (int c = 0; c < D4_CH; ++c) {
             if (c0 + c < a.C) {
-                const float* s = src + c * plane;
+                const float* s = src + band[c];
                 f32x4 o;
                 o[0] = s[x[0]]; o[1] = s[x[1]]; o[2] = s[x[2]]; o[3] = s[x[3]];
                 *reinterpret_cast<f32x4*>(dst + c * tplane) = o;
@@ -93,7 +103,7 @@ __global__ __launch_bounds__(256) void d4_gather_kernel(D4GatherDev a) {
 #pragma unroll
         for (int c = 0; c < D4_LC; ++c) {
             if (c0 + h + c < a.C) {
-                const float* s = src + (h + c) * plane + col;
+                const float* s = src + band[h + c] + col;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) lds[c][lp0 + 8 * k][lq] = s[rows[k]];
             }
@@ -109,6 +119,18 @@ __global__ __launch_bounds__(256) void d4_gather_kernel(D4GatherDev a) {
             }
         }
     }
+}
+
+// grid (max(ceil(th * tw/4 / 256), ceil(th/32) * ceil(tw/32)), ceil(C / D4_CH), count)
+__global__ __launch_bounds__(256) void d4_gather_kernel(D4GatherDev a) {
+    __shared__ float lds[D4_LC][D4_S][D4_P];
+    d4_gather_body(a, lds, false);
+}
+
+// the same grid; origins [n_tiles][3]
+__global__ __launch_bounds__(256) void bands_gather_kernel(D4GatherDev a) {
+    __shared__ float lds[D4_LC][D4_S][D4_P];
+    d4_gather_body(a, lds, true);
 }
 
 struct D4FoldDev {
@@ -235,8 +257,32 @@ extern "C" int mphsir_scene_gather_d4(const mphsir_scene_gather_d4_args* a, void
     const long quads = (long)a->th * (a->tw / 4), chunks = (a->C + D4_CH - 1) / D4_CH;
     MPHSIR_REQUIRE(quads < (1L << 30) && (long)a->H * a->W < (1L << 31) && chunks <= 65535, "scene_gather_d4: scene or tile too large");
     const long squares = (long)((a->th + D4_S - 1) / D4_S) * ((a->tw + D4_S - 1) / D4_S), lin = (quads + 255) / 256;
-    D4GatherDev d{a->scene, a->origins, a->tiles, a->j0, a->n_tiles, a->G * a->n_tiles - 1, a->modes_packed, a->C, a->H, a->W, a->th, a->tw};
+    D4GatherDev d{a->scene, a->origins, a->tiles, a->j0, a->n_tiles, a->G * a->n_tiles - 1, a->modes_packed, a->C, a->C, a->H, a->W, a->th, a->tw};
     MPHSIR_LAUNCH(MPHSIR_K_SCENE, d4_gather_kernel, dim3((unsigned)(lin > squares ? lin : squares), (unsigned)chunks, (unsigned)a->count), dim3(256),
+                  0, reinterpret_cast<hipStream_t>(stream), d);
+    return MPHSIR_OK;
+}
+
+extern "C" int mphsir_scene_gather_bands(const mphsir_scene_gather_bands_args* a, void* stream) {
+    using namespace mphsir;
+    clear_error();
+    MPHSIR_CHECK_ARGS(a, "scene_gather_bands");
+    MPHSIR_REQUIRE(a->scene && a->origins && a->tiles, "scene_gather_bands: null pointer");
+    MPHSIR_REQUIRE(a->count > 0 && a->count <= 65535 && a->C > 0 && a->Cs > 0 && a->H > 0 && a->W > 0,
+                   "scene_gather_bands: bad sizes (count %d, C %d, Cs %d, H %d, W %d; count <= 65535)", a->count, a->C, a->Cs, a->H, a->W);
+    MPHSIR_REQUIRE(d4_modes_ok(a->G, a->modes_packed),
+                   "scene_gather_bands: G %d must be 1, 2, 4 or 8 and modes_packed 0x%x hold 3 bits for each of the G passes", a->G, a->modes_packed);
+    MPHSIR_REQUIRE(a->n_tiles > 0 && a->n_tiles < (1 << 24) && a->j0 >= 0 && a->j0 < a->G * a->n_tiles,
+                   "scene_gather_bands: item %d outside the %d x %d items", a->j0, a->G, a->n_tiles);
+    MPHSIR_REQUIRE(a->th > 0 && a->tw > 0 && a->th % 4 == 0 && a->tw % 4 == 0 && aligned16(a->tiles),
+                   "scene_gather_bands: tile %d x %d must be multiples of 4 and the tile buffer 16-byte aligned", a->th, a->tw);
+    MPHSIR_REQUIRE(a->th == a->tw || !d4_transposes(a->G, a->modes_packed),
+                   "scene_gather_bands: a transposing mode (2, 3, 6, 7) needs a square tile, got %d x %d", a->th, a->tw);
+    const long quads = (long)a->th * (a->tw / 4), chunks = (a->C + D4_CH - 1) / D4_CH;
+    MPHSIR_REQUIRE(quads < (1L << 30) && (long)a->H * a->W < (1L << 31) && chunks <= 65535, "scene_gather_bands: scene or tile too large");
+    const long squares = (long)((a->th + D4_S - 1) / D4_S) * ((a->tw + D4_S - 1) / D4_S), lin = (quads + 255) / 256;
+    D4GatherDev d{a->scene, a->origins, a->tiles, a->j0, a->n_tiles, a->G * a->n_tiles - 1, a->modes_packed, a->C, a->Cs, a->H, a->W, a->th, a->tw};
+    MPHSIR_LAUNCH(MPHSIR_K_SCENE, bands_gather_kernel, dim3((unsigned)(lin > squares ? lin : squares), (unsigned)chunks, (unsigned)a->count), dim3(256),
                   0, reinterpret_cast<hipStream_t>(stream), d);
     return MPHSIR_OK;
 }

@@ -914,6 +914,48 @@ def scene_fold_d4(y, store, j0, count, modes):
     return store
 
 
+def scene_gather_bands(scene, origins3, C, th, tw, j0, modes, out):
+    """scene (Cs,H,W) fp32, origins3 (N, 3) int32 on the device (rows (ob, oy, ox), exactly one per item of the plan), out (count,C,th,tw)
+    fp32: out[i] = item j = min(j0 + i, G * N - 1) of the pass-major list j = g * N + s, the C-band window of the scene cut at origins3[s]
+    through the mirror map on all three axes, under mode modes[g] (include/mphsir_bands.h).  modes = (0,) is the plain cut; one launch,
+    a bitwise copy."""
+    lib = _lib.load()
+    _check(scene, origins3, out)
+    assert scene.dim() == 3 and scene.dtype == torch.float32 and scene.is_contiguous()
+    assert origins3.dim() == 2 and origins3.shape[1] == 3 and origins3.dtype == torch.int32 and origins3.is_contiguous()
+    Cs, H, W = scene.shape
+    G, packed = pack_d4_modes(modes)
+    assert out.dim() == 4 and out.shape[1:] == (C, th, tw) and out.dtype == torch.float32 and out.is_contiguous() and out.device == scene.device
+    a = _lib.SceneGatherBandsArgs(scene=_p(scene), origins=_p(origins3), tiles=_p(out), j0=j0, count=out.shape[0], n_tiles=origins3.shape[0], G=G,
+                                  modes_packed=packed, C=C, Cs=Cs, H=H, W=W, th=th, tw=tw)
+    _lib.check(lib.mphsir_scene_gather_bands(ctypes.byref(a), _stream(scene)), "scene_gather_bands")
+    _acct("scene", 0.0, 8.0 * out.numel())
+    return out
+
+
+def scene_blend_bands(tiles, ob, oy, ox, ov, ovb, Cs, H, W, clamp01=False, out=None):
+    """tiles (nb*ny*nx,C,th,tw) fp32 numbered (ib * ny + iy) * nx + ix, per-axis origins ob (nb,), oy (ny,), ox (nx,) int32 on the device
+    -> (Cs,H,W) fp32: every element the ramp-weighted mean of the items that cover it, the ramps of scene_blend_tiles on the two
+    spatial axes (ov) and the same ramp on the band axis (ovb); item bands beyond Cs are never read (include/mphsir_bands.h).  One
+    deterministic launch."""
+    lib = _lib.load()
+    _check(tiles, ob, oy, ox, out)
+    assert tiles.dim() == 4 and tiles.dtype == torch.float32 and tiles.is_contiguous()
+    assert ob.dim() == oy.dim() == ox.dim() == 1 and ob.dtype == oy.dtype == ox.dtype == torch.int32
+    assert ob.is_contiguous() and oy.is_contiguous() and ox.is_contiguous()
+    n, C, th, tw = tiles.shape
+    nb, ny, nx = ob.shape[0], oy.shape[0], ox.shape[0]
+    assert n == nb * ny * nx, "tile store holds %d items, the origin arrays describe %d x %d x %d" % (n, nb, ny, nx)
+    if out is None:
+        out = torch.empty((Cs, H, W), dtype=torch.float32, device=tiles.device)
+    assert out.shape == (Cs, H, W) and out.dtype == torch.float32 and out.is_contiguous() and out.device == tiles.device
+    a = _lib.SceneBlendBandsArgs(tiles=_p(tiles), ob=_p(ob), oy=_p(oy), ox=_p(ox), scene=_p(out), nb=nb, ny=ny, nx=nx, C=C, Cs=Cs, H=H, W=W,
+                                 th=th, tw=tw, ov=ov, ovb=ovb, clamp01=1 if clamp01 else 0)
+    _lib.check(lib.mphsir_scene_blend_bands(ctypes.byref(a), _stream(tiles)), "scene_blend_bands")
+    _acct("scene", 0.0, 4.0 * (tiles.numel() + out.numel()))
+    return out
+
+
 def quality_bands(restored, clean, out=None):
     """restored, clean (B,C,H,W) fp32 (or (C,H,W): B = 1) -> (psnr (B,C) f64, ssim (B,C) f64, sam_deg (B,) f64, sam_pixels (B,) i64) on
     the inputs' device: band-wise PSNR / SSIM (skimage's, data_range 1) and the mean spectral angle in degrees with the number of pixels

@@ -39,6 +39,11 @@ Mode 13 measures the cube through the coded aperture --cassi_mask (a .mat with a
 max(256, H) x max(256, W)) at a crop origin drawn from --seed, with the tensor form (degrade.cassi_measure) or, under --fused_degrade 1,
 the HIP launch pair (ops.cassi): the same values either way, since the measurement has no per-element draws.  A mask file smaller
 than the cube ends the run with a message.
+A cube whose band count is not the model's (Urban's 210 bands under the 100-band model, say) is degraded and scored on its own bands and
+restored through windows along the spectral axis (an addition: scene.SceneRestorer(bands=...), --band_overlap; windows of the model's band
+count, blended with linear ramps, one mirror-padded window for a cube with fewer bands): with --tile as windows x tiles, without it as one
+spatial tile, the cropped cube.  What windows cost in quality is unmeasured.  Mode 13 collapses the bands into one measurement and ends
+the run with a message for such a cube, as does mode 9 beyond the 100 bands of its wavelength table.
 --ckpt_path evaluates a Lightning checkpoint of the reference (`net.` key prefix).
 """
 import argparse
@@ -105,6 +110,9 @@ def build_parser():
     p.add_argument("--task_classes", type=int, default=0, help="0: the model's own task set (6 / 7); 1: the one-task net of the cassi fine-tune (mode 13)")
     p.add_argument("--cassi_mask", type=str, default="", help="mode 13: coded-aperture mask, a .mat ('mask') or .npy file; default: a seeded binary mask")
     p.add_argument("--cassi_step", type=int, default=2, help="mode 13: dispersion step in columns per band (the reference: 2)")
+    p.add_argument("--band_overlap", type=int, default=-1, help="a cube whose band count is not the model's is restored through windows along the "
+                   "spectral axis (scene.SceneRestorer(bands=...)): nominal overlap of neighbouring windows in bands, at most bands // 2; "
+                   "-1 (default): bands // 4 -- the default of an option, not a tuned value")
     p.add_argument("--save_restored", type=int, default=0, help="1: write <output_path>/<mode label>/restored_<name>.npy (fp32, (C,H,W))")
     return p
 
@@ -223,8 +231,11 @@ def scene_restorer(o, net, cache, name, H, W):
     T, ov = (o.tile, o.tile_overlap) if o.tile > 0 else (max(H, W), 0)
     if T not in cache:
         try:
-            cache[T] = SceneRestorer(net, tile=T, overlap=ov, ensemble=o.ensemble)   # tiles of one shape: one captured forward serves every scene
+            cache[T] = SceneRestorer(net, tile=T, overlap=ov, ensemble=o.ensemble,    # tiles of one shape: one captured forward serves every scene
+                                     band_overlap=None if o.band_overlap < 0 else o.band_overlap)
         except ValueError as e:
+            if "band overlap" in str(e):
+                raise SystemExit("--band_overlap %d: %s" % (o.band_overlap, e))
             if o.tile > 0:
                 raise SystemExit("--tile %d --tile_overlap %d: %s" % (o.tile, o.tile_overlap, e))
             raise SystemExit("cube %s is %d x %d: --ensemble %d restores it as one %d x %d tile: %s" % (name, H, W, o.ensemble, T, T, e))
@@ -233,6 +244,17 @@ def scene_restorer(o, net, cache, name, H, W):
         raise SystemExit("cube %s is %d x %d and is restored as %d x %d tiles: --ensemble 8 turns tiles by 90 degrees and needs square ones "
                          "(use --ensemble 4: the flips and the half turn)" % (name, H, W, p.th, p.tw))
     return cache[T]
+
+
+def check_other_band_count(o, name, Cs, bands):
+    """a cube of Cs bands under a model of `bands`: degraded and scored on its own Cs bands, restored through spectral windows -- unless the
+    mode's degradation is not defined for that band count"""
+    if o.mode == 13:
+        raise SystemExit("cube %s has %d bands, the model %d: mode 13 (the CASSI measurement) collapses the bands into one measurement "
+                         "and cannot be restored through spectral windows" % (name, Cs, bands))
+    if o.mode == 9 and Cs > 100:
+        raise SystemExit("cube %s has %d bands: mode 9 (haze) takes its wavelengths from a table of 100 bands and is not defined "
+                         "beyond them" % (name, Cs))
 
 
 def evaluate(o, net, dev):
@@ -266,6 +288,9 @@ def evaluate_quality(o, net, dev):
     for name, clean, real in cube_source(o, cfg_bands, dev, gen):
         if o.tile > 0:
             check_whole_scene(o, name, clean)
+        windows = clean.shape[1] != cfg_bands          # another band count: spectral windows, through the restorer with or without --tile
+        if windows:
+            check_other_band_count(o, name, clean.shape[1], cfg_bands)
         if o.mode == 12:
             degraded, pid = real, 1
         elif fused_degrader is not None:
@@ -277,7 +302,7 @@ def evaluate_quality(o, net, dev):
                 raise SystemExit(str(e))                    # a mask file smaller than the cube
         else:
             degraded, pid = degrade_for_mode(o, clean, d, o.model)
-        if scenes:
+        if scenes or windows:
             restored = scene_restorer(o, net, restorers, name, *clean.shape[-2:])(degraded.float().contiguous(), pid)
         else:
             restored = run(degraded.float().contiguous(), torch.tensor([pid], device=dev))
